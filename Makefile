@@ -19,8 +19,8 @@ test-gpu:         ## GPU kernel numerics + engine tests (MI355X box)
 test-integration: ## controller integration tests only
 	$(PY) -m pytest tests/test_controller_integration.py tests/test_client_cli.py -q
 
-bench:            ## flagship single-GPU bench (driver contract)
-	$(PY) bench.py --gpus 1
+bench:            ## flagship single-GPU bench (driver contract), both metrics
+	$(PY) bench.py --gpus 1 --full
 
 images:           ## build all workload container images
 	docker build -f images/base.Dockerfile -t runbooks-amd/base:latest .

@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """Flagship benchmark for the driver contract.
 
-Default (--mode both) emits BOTH BASELINE.json headline metrics as
-sequential JSON lines: the llama2-7b LoRA fine-tune step (DP over
-RCCL/xGMI, "finetune samples/sec") first, then "Server tokens/sec"
-(paged-KV batch-32 decode on the same model), bf16, synthetic token
-data, random-init weights. The reference publishes no numbers; this
-bench ESTABLISHES the baseline. --mode train / serve
-select a single metric.
+A plain run measures the headline figure only and prints ONE JSON line:
+"Server tokens/sec" (paged-KV batch-32 decode of llama2-7b), bf16,
+synthetic prompts, random-init weights. --full additionally runs the
+llama2-7b LoRA fine-tune step (DP over RCCL/xGMI, "finetune
+samples/sec") first and prints its line before the serve line, so both
+BASELINE.json metrics come out as sequential JSON lines. The reference
+publishes no numbers; this bench ESTABLISHES the baseline
+(BASELINE.md). --mode train / serve / both selects explicitly.
+
+--dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (see _dump_outputs); inputs are seeded, so two builds
+run with the same arguments can be compared array for array.
 
 Launch (driver):
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus 1 --steps K --warmup W --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -72,6 +78,30 @@ def _max_over_ranks(x: float) -> float:
     return x
 
 
+# --dump-outputs writes at most 64 MB per run: the serve arrays share
+# 60 MB, which leaves room for train_loss (--full) and the .npy headers
+_DUMP_BUDGET = 60 << 20
+
+
+def _dump_outputs(out_dir: str, arrays: dict) -> None:
+    """Write each array as out_dir/<name>.npy (float32; float64 inputs
+    stay float64). The arrays share the budget above evenly; one
+    that is over its share is replaced by a fixed, seeded sample of its
+    flattened elements, so two runs still compare element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = _DUMP_BUDGET // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.random.default_rng(17).choice(
+                a.size, size=share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def bench_train(args) -> dict:
     from runbooks_amd.models import get_config
     from runbooks_amd.train import TrainConfig, Trainer
@@ -94,12 +124,18 @@ def bench_train(args) -> dict:
         trainer.train_step(batches[i % len(batches)])
     comm.barrier()
     _sync()
+    losses = []
     t0 = time.perf_counter()
     for i in range(args.steps):
-        trainer.train_step(batches[i % len(batches)])
+        losses.append(trainer.train_step(batches[i % len(batches)]))
     comm.barrier()
     _sync()
     dt = _max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and comm.rank() == 0:
+        # train_step returns the loss: one value per timed step
+        import numpy as np
+        _dump_outputs(args.dump_outputs,
+                      {"train_loss": np.asarray(losses, dtype=np.float64)})
 
     n = comm.world_size()
     samples = args.steps * args.micro_batch * n
@@ -148,6 +184,22 @@ def bench_serve(args) -> dict:
         prompt = torch.randint(0, vocab, (prompt_len,), generator=g).tolist()
         eng.submit(prompt, max_new_tokens=1 << 30)  # run until bench ends
 
+    last = {}
+    if args.dump_outputs:
+        # keep a reference to the logits each decode step hands to the
+        # sampler (no copy, no extra GPU work): after the timed loop it
+        # holds the last step's logits
+        sample = eng._sample_batch
+
+        def tapped(logits, reqs):
+            last["logits"] = logits
+            return sample(logits, reqs)
+        eng._sample_batch = tapped
+
+    def emitted():
+        # every prefill and every decoded row yields one token
+        return eng.stats["prefills"] + eng.stats["decode_tokens"]
+
     for _ in range(args.serve_batch):
         new_req()
     # warmup: prefill everyone + W decode steps
@@ -156,14 +208,28 @@ def bench_serve(args) -> dict:
     assert len(eng.running) == args.serve_batch
     _sync()
     t0 = time.perf_counter()
-    tokens = 0
+    before = emitted()
     for _ in range(args.steps):
-        before = sum(len(r.output_ids) for r in eng.running)
-        eng.step()
-        after = sum(len(r.output_ids) for r in eng.running)
-        tokens += after - before
+        # a sequence that reaches the model's max_seq_len finishes; a
+        # fresh prompt takes its place so every timed step has work
+        for _done in eng.step():
+            new_req()
     _sync()
     dt = time.perf_counter() - t0
+    tokens = emitted() - before
+    if args.dump_outputs:
+        # what a caller of step() receives: the token ids appended to
+        # each running request (the trailing ones every request has),
+        # plus the logits they were sampled from in the last step
+        import numpy as np
+        reqs = sorted(eng.running, key=lambda r: r.request_id)
+        t = min([len(r.output_ids) for r in reqs] + [args.steps])
+        arrays = {"serve_tokens": np.asarray(
+            [r.output_ids[len(r.output_ids) - t:] for r in reqs],
+            dtype=np.float64)}
+        if "logits" in last:
+            arrays["serve_logits"] = last["logits"].float().cpu().numpy()
+        _dump_outputs(args.dump_outputs, arrays)
     if comm.is_dist() and comm.world_size() > 1:
         from runbooks_amd.serve.tp_worker import broadcast_shutdown
         broadcast_shutdown(torch.device(eng.device))
@@ -195,7 +261,15 @@ def main():
     p.add_argument("--steps", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--mode", choices=["both", "train", "serve"],
-                   default="both")
+                   default=None,
+                   help="default: serve (the headline figure); both "
+                        "with --full")
+    p.add_argument("--full", action="store_true",
+                   help="also run the fine-tune benchmark and print its "
+                        "JSON line before the serve line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as "
+                        "DIR/<name>.npy (at most 64 MB in all)")
     p.add_argument("--model", default=None)
     p.add_argument("--seq-len", type=int, default=512)
     p.add_argument("--micro-batch", type=int, default=4)
@@ -209,6 +283,8 @@ def main():
                         "headline config — reported with "
                         "dtype=bf16+fp8-kv)")
     args = p.parse_args()
+    if args.mode is None:
+        args.mode = "both" if args.full else "serve"
     if args.model is None:
         if torch.cuda.is_available():
             args.model = "llama2-7b"
@@ -221,9 +297,9 @@ def main():
     comm.init_from_env()
     torch.manual_seed(17)
 
-    # Default emits BOTH headline metrics sequentially (BASELINE.json:
+    # --full emits BOTH headline metrics sequentially (BASELINE.json:
     # "Server tokens/sec + finetune samples/sec") — one JSON line each,
-    # finetune first, serve last.
+    # finetune first, serve last. A plain run emits the serve line only.
     results = []
     if args.mode in ("both", "train"):
         results.append(bench_train(args))

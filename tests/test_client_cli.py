@@ -219,14 +219,14 @@ def test_trainer_main_end_to_end(tmp_path, monkeypatch):
 
 
 def test_bench_contract_cpu(tmp_path):
-    """bench.py default emits BOTH driver-contract JSON lines (finetune
+    """bench.py --full emits BOTH driver-contract JSON lines (finetune
     first, serve last — BASELINE.json names both headline metrics)."""
     import json as _json
     import subprocess
     import sys
 
     out = subprocess.run(
-        [sys.executable, "bench.py", "--steps", "2", "--warmup", "1",
+        [sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1",
          "--micro-batch", "2", "--seq-len", "16"],
         capture_output=True, text=True, timeout=240)
     assert out.returncode == 0, out.stderr[-800:]
@@ -249,6 +249,49 @@ def test_bench_contract_cpu(tmp_path):
     d = _json.loads(out.stdout.strip().splitlines()[-1])
     assert d["metric"] == "serve_tokens_per_sec"
     assert d["value"] > 0
+
+
+def test_bench_plain_run_dumps_outputs_cpu(tmp_path):
+    """A plain bench.py run prints the serve headline line only, honours
+    --steps, and --dump-outputs writes the last step's arrays; the same
+    arguments give the same arrays from run to run."""
+    import json as _json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        out = subprocess.run(
+            [sys.executable, "bench.py", "--gpus", "1", "--steps", "3",
+             "--warmup", "1", "--serve-batch", "2", "--prompt-len", "8",
+             "--dump-outputs", str(tmp_path / name)],
+            capture_output=True, text=True, timeout=240)
+        assert out.returncode == 0, out.stderr[-800:]
+        lines = [ln for ln in out.stdout.strip().splitlines()
+                 if ln.startswith("{")]
+        assert len(lines) == 1
+        d = _json.loads(lines[0])
+        assert d["metric"] == "serve_tokens_per_sec"
+        assert d["steps"] == 3 and d["warmup"] == 1
+        assert d["ms_per_step"] > 0
+        # 2 sequences x 3 timed decode steps
+        assert abs(d["value"] * d["ms_per_step"] * 3 / 1e3 - 6) < 1e-6
+        files = sorted(p.name for p in (tmp_path / name).iterdir())
+        assert files == ["serve_logits.npy", "serve_tokens.npy"]
+        dumps.append({f: np.load(tmp_path / name / f) for f in files})
+    a, b = dumps
+    assert a["serve_tokens.npy"].shape == (2, 3)
+    assert a["serve_logits.npy"].shape[0] == 2
+    assert a["serve_logits.npy"].dtype == np.float32
+    assert np.isfinite(a["serve_logits.npy"]).all()
+    # the dumped tokens are the argmax of the dumped logits (greedy)
+    assert (a["serve_logits.npy"].argmax(-1)
+            == a["serve_tokens.npy"][:, -1]).all()
+    assert np.array_equal(a["serve_tokens.npy"], b["serve_tokens.npy"])
+    np.testing.assert_allclose(a["serve_logits.npy"], b["serve_logits.npy"],
+                               rtol=1e-5, atol=1e-6)
 
 
 def test_tui_components():
