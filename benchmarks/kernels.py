@@ -167,6 +167,7 @@ def main():
                    2 * yb.numel() * 2))
 
     # decode GEMMs: fresh weights per call (no L3 reuse)
+    from runbooks_amd.ops.linear import _W4_REGISTRY, quantize_int4
     for N, K in [(12288, 4096), (4096, 4096), (22016, 4096), (4096, 11008),
                  (32000, 4096)]:
         xs = torch.randn(32, K, dtype=bf16, device=dev)
@@ -197,6 +198,24 @@ def main():
         out.append(row(f"decode_gemm_v2", f"32x{N}x{K}", us, N * K * 2,
                        flops=2 * 32 * N * K))
         del sws
+        # int4 weight-only kernel (MODEL_LOAD_IN_4BIT): group-64 nibbles
+        # + bf16 scales, same pre-swizzled x operand. 10 sets of 9-65 MB
+        # would sit in the 256 MiB Infinity Cache, so rotate >= 600 MB.
+        w4_bytes = N * K // 2 + N * K // 64 * 2
+        n4 = max(10, -(-600_000_000 // w4_bytes))
+        q4 = [ops.ext().w4_swizzle(*quantize_int4(
+            ws[j] if j < 10 else
+            torch.randn(N, K, dtype=bf16, device=dev))) for j in range(n4)]
+        _W4_REGISTRY.clear()
+
+        def dgw4():
+            i[0] = (i[0] + 1) % n4
+            return ops.ext().decode_gemm_w4(sx, *q4[i[0]], 32, N, K)
+        us = timeit(dgw4)
+        out.append(row(f"decode_gemm_w4", f"32x{N}x{K}", us,
+                       N * K // 2 + N * K // 64 * 2,
+                       flops=2 * 32 * N * K))
+        del q4
 
     # fp8 decode GEMM
     from runbooks_amd.ops.linear import quantize_fp8

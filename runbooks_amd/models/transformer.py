@@ -434,7 +434,8 @@ class Transformer(nn.Module):
 
 
 def fuse_for_inference(model: "Transformer",
-                       load_in_8bit: bool = False) -> "Transformer":
+                       load_in_8bit: bool = False,
+                       load_in_4bit: bool = False) -> "Transformer":
     """Fuse each block's QKV and gate/up weights into single tensors for
     serving: one wide GEMM per group instead of 2-3 skinny ones (the
     batch-<=32 decode GEMMs are weight-bandwidth bound, and hipBLASLt is
@@ -477,7 +478,8 @@ def fuse_for_inference(model: "Transformer",
             mlp.up_proj.weight = nn.Parameter(fused[half:],
                                               requires_grad=False)
 
-    if not load_in_8bit and torch.cuda.is_available() and ops.has_hip() and \
+    if not load_in_8bit and not load_in_4bit and \
+            torch.cuda.is_available() and ops.has_hip() and \
             _os.environ.get("RB_DECODE_GEMM", "1") == "1":
         # Register fragment-lane-major weight copies for the v2 decode
         # GEMM (csrc/decode_gemm.hip): doubles decode-weight memory, which
@@ -523,6 +525,25 @@ def fuse_for_inference(model: "Transformer",
         if model.lm_head.weight.shape[0] % 64 == 0 and \
                 model.lm_head.weight.shape[1] % 256 == 0:
             quantize_fp8(model.lm_head.weight)
+
+    if load_in_4bit and torch.cuda.is_available():
+        # MODEL_LOAD_IN_4BIT: the same decode weight set additionally
+        # stored as group-64 int4 + bf16 scales (4.25 bits/weight) for
+        # ops/csrc/decode_gemm_w4.hip. bf16 masters stay for prefill and
+        # m > 32, the same both-copies trade as the fp8 branch.
+        from ..ops.linear import quantize_int4
+        ext = ops.ext()
+        for blk in model.blocks:
+            for w in (getattr(blk.attn, "_qkv_w", None),
+                      getattr(blk.mlp, "_gateup_w", None),
+                      blk.attn.o_proj.weight,
+                      blk.mlp.down_proj.weight):
+                if w is not None and ext.decode_gemm_w4_supported(
+                        32, w.shape[0], w.shape[1]):
+                    quantize_int4(w)
+        if ext.decode_gemm_w4_supported(32, model.lm_head.weight.shape[0],
+                                        model.lm_head.weight.shape[1]):
+            quantize_int4(model.lm_head.weight)
     return model
 
 

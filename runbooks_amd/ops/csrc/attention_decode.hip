@@ -870,10 +870,14 @@ std::vector<at::Tensor> paged_decode_swz(at::Tensor q, at::Tensor k_cache,
   TORCH_CHECK(Hq % hkv == 0, "paged_decode: Hq % Hkv");
   const int G = Hq / hkv;
   auto out = at::empty_like(q);
-  // emit the o_proj operand layout only for decode-batch shapes
+  // emit the o_proj operand layout only for decode-batch shapes, and only
+  // where the chosen kernel writes it: the single-pass epilogues emit it
+  // in 8-element units (dh >= 128: >= 8 elements per merge lane), the
+  // split path's combine kernel for every dh. Otherwise return no
+  // operand (consumers swizzle themselves) rather than an unwritten one.
   c10::optional<at::Tensor> out_swz;
   const int B0 = (int)q.size(0);
-  if (B0 <= 32 && (Hq * dh) % 16 == 0) {
+  if (B0 <= 32 && (Hq * dh) % 16 == 0 && (dh >= 128 || nsplit > 1)) {
     out_swz = at::empty({(int64_t)(Hq * dh / 16) * 512}, q.options());
   }
   auto stream = at::hip::getCurrentHIPStream();

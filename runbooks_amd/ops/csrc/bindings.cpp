@@ -59,6 +59,11 @@ at::Tensor decode_swizzle_x(at::Tensor x);
 int64_t decode_gemm_split(int64_t N, int64_t K);
 bool decode_gemm_supported(int64_t M, int64_t N, int64_t K);
 at::Tensor skinny_gemm_fp8(at::Tensor x, at::Tensor w8, at::Tensor scale);
+std::vector<at::Tensor> w4_swizzle(at::Tensor q, at::Tensor scales);
+at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
+                          int64_t M, int64_t N, int64_t K, int64_t force_split);
+int64_t decode_gemm_w4_split(int64_t N, int64_t K);
+bool decode_gemm_w4_supported(int64_t M, int64_t N, int64_t K);
 int64_t skinny_gemm_mmax();
 at::Tensor qkv_rope_append(at::Tensor y, at::Tensor cos, at::Tensor sin,
                            at::Tensor positions, at::Tensor k_cache,
@@ -138,6 +143,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "EXPERIMENTAL 256^2 8-phase bf16 GEMM (C = A @ B^T)");
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8,
         "fp8-e4m3 weight-only decode GEMM with per-channel scales");
+  m.def("w4_swizzle", &w4_swizzle,
+        "one-time canonical int4 (q, scales) -> fragment-lane-major layout");
+  m.def("decode_gemm_w4", &decode_gemm_w4,
+        "int4 weight-only decode GEMM (group-64 bf16 scales): "
+        "y[M<=32,N] = x @ dequant(Wq)^T (bf16)",
+        py::arg("xs"), py::arg("wq_swz"), py::arg("sc_swz"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("force_split") = -1);
+  m.def("decode_gemm_w4_split", &decode_gemm_w4_split);
+  m.def("decode_gemm_w4_supported", &decode_gemm_w4_supported);
   m.def("qkv_rope_append", &qkv_rope_append,
         "packed qkv -> rope'd q + rope'd k / v appended to the paged cache");
   m.def("swiglu_packed", &swiglu_packed,

@@ -80,6 +80,79 @@ def dequantize_fp8(w8_bytes: torch.Tensor, scale: torch.Tensor,
             scale[:, None]).to(dtype)
 
 
+# data_ptr(weight) -> (wq_swz, sc_swz, (N, K), weakref to the registered
+# tensor): the int4 kernel layout of csrc/decode_gemm_w4.hip. Populated by
+# quantize_int4 (serving with MODEL_LOAD_IN_4BIT); same keying and
+# weakref-identity rule as the registries above (see _registry_get).
+_W4_REGISTRY: dict[int, tuple] = {}
+
+W4_GROUP = 64
+
+
+def _w4_codes(weight: torch.Tensor):
+    if weight.dim() != 2 or weight.shape[1] % W4_GROUP != 0:
+        raise ValueError(f"int4 quantization needs [N, K] with K % "
+                         f"{W4_GROUP} == 0, got {tuple(weight.shape)}")
+    n, k = weight.shape
+    w =weight.detach().float().reshape(n, k // W4_GROUP, W4_GROUP)
+    scales = (w.abs().amax(dim=2).clamp(min=1e-8) / 7).to(torch.bfloat16)
+    codes = torch.round(w / scales.float()[:, :, None]).clamp_(-8, 7)
+    return codes.reshape(n, k), scales
+
+
+@torch.no_grad()
+def quantize_int4(weight: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Symmetric group-wise int4 along K (groups of 64): scale[n, g] =
+    bf16(max(absmax, 1e-8) / 7), code = clamp(round(w / scale), -8, 7),
+    stored nibble = code + 8. Returns the canonical pair: q uint8
+    [N, K/2] (byte k/2 = even k in the low nibble, odd k in the high
+    nibble) and scales bf16 [N, K/64].
+
+    On a GPU tensor it also builds the decode kernel's layout
+    (csrc/decode_gemm_w4.hip) and registers it so fast_linear dispatches
+    to the int4 decode GEMM. Pass the PERSISTENT tensor object
+    (Parameter / fused buffer), not .data — lookups verify identity via
+    weakref."""
+    codes, scales = _w4_codes(weight)
+    nib = (codes + 8).to(torch.uint8)
+    q = (nib[:, 0::2] | (nib[:, 1::2] << 4)).contiguous()
+    scales = scales.contiguous()
+    if _backend.use_hip(weight):
+        ext = _backend.ext()
+        n, k = int(weight.shape[0]), int(weight.shape[1])
+        if ext.decode_gemm_w4_supported(32, n, k):
+            for ptr in [p for p, e in _W4_REGISTRY.items()
+                        if e[-1]() is None]:
+                del _W4_REGISTRY[ptr]          # purge dead entries
+            wq_swz, sc_swz = ext.w4_swizzle(q, scales)
+            _W4_REGISTRY[weight.data_ptr()] = (wq_swz, sc_swz, (n, k),
+                                               weakref.ref(weight))
+    return q, scales
+
+
+def dequantize_int4(q: torch.Tensor, scales: torch.Tensor,
+                    dtype=torch.bfloat16) -> torch.Tensor:
+    """(code * float(scale)).to(dtype) from the canonical pair. With
+    dtype=bfloat16 (round-to-nearest-even) this is the exact weight the
+    int4 decode kernel multiplies by."""
+    n, kh = q.shape
+    codes = torch.stack([q & 0xF, q >> 4], dim=2).reshape(n, 2 * kh)
+    codes = codes.float() - 8.0
+    w = codes.reshape(n, -1, W4_GROUP) * scales.float()[:, :, None]
+    return w.reshape(n, 2 * kh).to(dtype)
+
+
+@torch.no_grad()
+def fake_quantize_int4_(weight: torch.Tensor) -> torch.Tensor:
+    """In-place dequantize(quantize(w)); registers nothing. For tests and
+    offline quality evaluation of the 4-bit format."""
+    codes, scales = _w4_codes(weight)
+    n, k = weight.shape
+    w = codes.reshape(n, -1, W4_GROUP) * scales.float()[:, :, None]
+    weight.copy_(w.reshape(n, k).to(weight.dtype))
+    return weight
+
+
 def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                 bias: torch.Tensor | None = None) -> torch.Tensor:
     if (bias is None and not torch.is_grad_enabled()
@@ -89,6 +162,18 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
         m = x.numel() // k
         n = weight.shape[0]
         if m <= 32:
+            if _W4_REGISTRY:
+                q4 = _registry_get(_W4_REGISTRY, weight)
+                if q4 is not None and \
+                        _backend.ext().decode_gemm_w4_supported(m, n, k):
+                    # same operand contract as the bf16 v2 branch below
+                    xs = getattr(x, "_rb_swz", None)
+                    if xs is None:
+                        xs = _backend.ext().decode_swizzle_x(
+                            x.reshape(m, k).contiguous())
+                    y = _backend.ext().decode_gemm_w4(xs, q4[0], q4[1],
+                                                      m, n, k)
+                    return y.view(*x.shape[:-1], n)
             if n % 64 == 0 and k % 256 == 0:
                 q = _registry_get(_FP8_REGISTRY, weight)
                 if q is not None:

@@ -99,13 +99,17 @@ class Engine:
                  dtype=torch.bfloat16, kv_blocks: int | None = None,
                  max_batch: int = 64, mem_fraction: float = 0.85, seed: int = 0,
                  load_in_8bit: bool = False, prefix_cache: bool | None = None,
-                 kv_fp8: bool | None = None):
+                 kv_fp8: bool | None = None, load_in_4bit: bool = False):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
             model = build_model(model, dtype=dtype, seed=seed,
                                 device=self.device)
         self.model = model.to(self.device).eval()
+        if load_in_4bit and load_in_8bit:
+            print("engine: MODEL_LOAD_IN_4BIT and MODEL_LOAD_IN_8BIT both "
+                  "set; serving 4-bit", flush=True)
+            load_in_8bit = False
         if torch.cuda.is_available():
             # TP>1 included: each rank fuses ITS OWN qkv / gate-up weight
             # shards and registers decode-GEMM layouts for them — the
@@ -113,7 +117,12 @@ class Engine:
             # so the worker-follow protocol stays aligned.
             from ..models.transformer import fuse_for_inference
             fuse_for_inference(self.model,
-                               load_in_8bit=load_in_8bit and model.tp == 1)
+                               load_in_8bit=load_in_8bit and model.tp == 1,
+                               load_in_4bit=load_in_4bit and model.tp == 1)
+        if load_in_4bit and model.tp > 1:
+            print("engine: MODEL_LOAD_IN_4BIT ignored at TP>1 "
+                  "(int4 decode path is single-GPU, like the fp8 one)",
+                  flush=True)
         if load_in_8bit and model.tp > 1:
             print("engine: MODEL_LOAD_IN_8BIT ignored at TP>1 "
                   "(fp8 decode path is single-GPU; 288 GB/GPU rarely "

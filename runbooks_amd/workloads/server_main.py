@@ -5,10 +5,12 @@ examples/llama2-7b/server.yaml, container-contract.md:50-56) — loads
 /content/model, serves an OpenAI-style completions API on :8080 with
 "/" readiness. Honors the contract env knobs:
 
-- MODEL_LOAD_IN_8BIT / MODEL_LOAD_IN_4BIT: weight quantization hints
-  (reference examples/llama2-7b/server.yaml:9). This runtime maps 8-bit
-  to fp8 storage when available and otherwise serves bf16 (288 GB HBM3E
-  rarely needs it).
+- MODEL_LOAD_IN_8BIT / MODEL_LOAD_IN_4BIT ("1" or "true"): weight-only
+  quantized decode (reference examples/llama2-7b/server.yaml:9,
+  llama2-70b/server.yaml:9). 8-bit stores fp8-e4m3 + per-channel scales,
+  4-bit stores group-64 int4 + bf16 scales; both keep the bf16 masters
+  for prefill. 4-bit wins when both are set; both apply at TP=1 on a GPU
+  and are otherwise ignored (bf16 serving).
 - TP: tensor parallelism degree (defaults to visible GPU count); ranks
   are spawned via torch.distributed.run over RCCL/xGMI.
 """
@@ -87,7 +89,9 @@ def main():
     kv_fp8 = os.environ.get("PARAM_KV_FP8",
                             os.environ.get("KV_FP8", "")).lower() in \
         ("1", "true")
-    engine = Engine(model, load_in_8bit=in_8bit, kv_fp8=kv_fp8)
+    in_4bit = os.environ.get("MODEL_LOAD_IN_4BIT", "").lower() in ("1", "true")
+    engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
+                    kv_fp8=kv_fp8)
     tok = load_tokenizer(model_dir if model_dir.exists() else None)
     if comm.rank() == 0:
         serve_forever(engine, tok, port=int(os.environ.get("PORT", "8080")),
