@@ -198,6 +198,36 @@ def main():
         out.append(row(f"decode_gemm_v2", f"32x{N}x{K}", us, N * K * 2,
                        flops=2 * 32 * N * K))
         del sws
+        # the same GEMM with its consumer fused into the epilogue, on
+        # the row-permuted layouts (llama2-7b: gate-up glu16, qkv rope16);
+        # same 10-weight rotation as the rows above
+        if (N, K) == (22016, 4096):
+            sws = [ops.ext().decode_swizzle_w_layout(w, 1) for w in ws]
+
+            def dgglu():
+                i[0] = (i[0] + 1) % 10
+                return ops.ext().decode_gemm_glu(sx, sws[i[0]], 32, N, K)
+            us = timeit(dgglu)
+            out.append(row("decode_gemm_swiglu", f"32x{N}x{K}", us,
+                           N * K * 2, flops=2 * 32 * N * K))
+            del sws
+        if (N, K) == (12288, 4096):
+            sws = [ops.ext().decode_swizzle_w_layout(w, 2, 32, 32, 128)
+                   for w in ws]
+            rc, rs = (t.to(dev) for t in ops.rope_tables(128, 4096, 10000.0))
+            kcr, vcr = ops.alloc_kv_cache(64, 32, 128, dev)
+            rpos = torch.arange(100, 132, dtype=torch.int32, device=dev)
+            rslot = torch.arange(32, dtype=torch.int32, device=dev) * BS
+
+            def dgrope():
+                i[0] = (i[0] + 1) % 10
+                return ops.ext().decode_gemm_rope_append(
+                    sx, sws[i[0]], 32, N, K, rc, rs, rpos, kcr, vcr, rslot,
+                    32)
+            us = timeit(dgrope)
+            out.append(row("decode_gemm_rope_append", f"32x{N}x{K}", us,
+                           N * K * 2, flops=2 * 32 * N * K))
+            del sws, kcr, vcr
         # int4 weight-only kernel (MODEL_LOAD_IN_4BIT): group-64 nibbles
         # + bf16 scales, same pre-swizzled x operand. 10 sets of 9-65 MB
         # would sit in the 256 MiB Infinity Cache, so rotate >= 600 MB.

@@ -127,9 +127,16 @@ class Attention(nn.Module):
             # fp8 caches take the generic path below (rope + fp8-quant
             # kv_append): that mode targets long-context KV-bound decode
             # where the attention read, not the epilogue, dominates.
-            y = ops.fast_linear(x, self._qkv_w)
-            q = ops.ext().qkv_rope_append(y, cos, sin, positions, kc, vc,
-                                          slot_mapping, self.hq)
+            if ops.fused_epilogue_ok(x, self._qkv_w, "rope16"):
+                # rope16 weight layout: the GEMM epilogue does the rope +
+                # append itself (csrc/decode_gemm.hip), no second kernel
+                q = ops.decode_linear_rope_append(
+                    x, self._qkv_w, cos, sin, positions, kc, vc,
+                    slot_mapping, self.hq)
+            else:
+                y = ops.fast_linear(x, self._qkv_w)
+                q = ops.ext().qkv_rope_append(y, cos, sin, positions, kc,
+                                              vc, slot_mapping, self.hq)
         else:
             q, k, v = self._qkv(x, cos, sin, positions)
             ops.kv_append(k, v, kc, vc, slot_mapping)
@@ -161,10 +168,28 @@ class MLP(nn.Module):
         self.down_proj = RowParallelLinear(cfg.intermediate_size, cfg.hidden_size,
                                            bias=cfg.mlp_bias, tp_size=tp, dtype=dtype)
 
+    def _glu_fused_epilogue(self, x, gelu):
+        """Decode hot path on a glu16 gate-up weight: the activation runs
+        in the gate-up GEMM's epilogue (csrc/decode_gemm.hip), which emits
+        the down-proj operand directly — no packed-GLU kernel, no
+        row-major h. None when the conditions do not hold."""
+        if not (self.down_proj.bias is None and
+                ops.fused_epilogue_ok(x, self._gateup_w, "glu16") and
+                ops.decode_layout(self.down_proj.weight) is not None):
+            return None
+        swz, m = ops.decode_linear_glu(x, self._gateup_w, gelu=gelu)
+        out, _ = ops.decode_linear_raw(None, self.down_proj.weight,
+                                       xs=swz, m=m)
+        return out
+
     def forward(self, x, slab_ok=False):
         if self.act == "silu_glu":
             if getattr(self, "_gateup_w", None) is not None and \
                     not torch.is_grad_enabled():
+                if slab_ok:
+                    out = self._glu_fused_epilogue(x, gelu=False)
+                    if out is not None:
+                        return out
                 y = ops.fast_linear(x, self._gateup_w)
                 if ops.use_hip(y):
                     I = y.shape[-1] // 2
@@ -187,6 +212,10 @@ class MLP(nn.Module):
             # csrc geglu_packed epilogue (GPU-validated r2).
             if getattr(self, "_gateup_w", None) is not None and \
                     not torch.is_grad_enabled():
+                if slab_ok:
+                    out = self._glu_fused_epilogue(x, gelu=True)
+                    if out is not None:
+                        return out
                 y = ops.fast_linear(x, self._gateup_w)
                 if ops.use_hip(y):
                     I = y.shape[-1] // 2
@@ -488,24 +517,38 @@ def fuse_for_inference(model: "Transformer",
         # guard: keep at least ~35% of the GPU free for KV cache.
         from ..ops.linear import register_decode_weight
         ext = ops.ext()
+        # Row-permuted copies where the shapes allow: the fused gate-up
+        # as glu16 and the fused qkv as rope16 let the GEMM epilogue do
+        # SwiGLU/GeGLU and RoPE + KV append in place (ops/linear.py).
         cands = []
         for blk in model.blocks:
-            for w in (getattr(blk.attn, "_qkv_w", None),
-                      getattr(blk.mlp, "_gateup_w", None),
-                      blk.attn.o_proj.weight,
-                      blk.mlp.down_proj.weight):
+            attn = blk.attn
+            gu = getattr(blk.mlp, "_gateup_w", None)
+            glu16 = gu is not None and (gu.shape[0] // 2) % 16 == 0
+            rope16 = model.cfg.pos == "rope" and (attn.dh // 2) % 16 == 0
+            for w, lay in (
+                    (getattr(attn, "_qkv_w", None),
+                     ("rope16", attn.hq, attn.hkv, attn.dh) if rope16
+                     else ("plain",)),
+                    (gu, ("glu16",) if glu16 else ("plain",)),
+                    (attn.o_proj.weight, ("plain",)),
+                    (blk.mlp.down_proj.weight, ("plain",))):
                 if w is not None and ext.decode_gemm_supported(
                         32, w.shape[0], w.shape[1]):
-                    cands.append(w)
+                    cands.append((w, lay))
         if model.lm_head.weight.shape[0] % 32 == 0 and \
                 ext.decode_gemm_supported(32, model.lm_head.weight.shape[0],
                                           model.lm_head.weight.shape[1]):
-            cands.append(model.lm_head.weight)
-        need = sum(2 * w.numel() for w in cands)
+            cands.append((model.lm_head.weight, ("plain",)))
+        need = sum(2 * w.numel() for w, _ in cands)
         free, total = torch.cuda.mem_get_info()
         if free - need >= int(0.35 * total):
-            for w in cands:
-                register_decode_weight(w)
+            for w, lay in cands:
+                register_decode_weight(w, *lay)
+            # the permuted swizzles go through a row-gathered temporary;
+            # hand those blocks back so the engine's KV-pool sizing sees
+            # the same free memory as with plain layouts
+            torch.cuda.empty_cache()
 
     if load_in_8bit and torch.cuda.is_available():
         # MODEL_LOAD_IN_8BIT: decode weights additionally stored as OCP

@@ -6,7 +6,17 @@ std::vector<at::Tensor> rmsnorm_fwd(at::Tensor x, at::Tensor w, double eps);
 std::vector<at::Tensor> rmsnorm_fwd_dec(at::Tensor x, at::Tensor w, double eps);
 std::vector<at::Tensor> rmsnorm_res_fwd_dec(at::Tensor x, at::Tensor res, at::Tensor w, double eps);
 std::vector<at::Tensor> rmsnorm_res_slab_fwd_dec(at::Tensor x, at::Tensor slabs, at::Tensor w, double eps);
-at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K);
+at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K,
+                           int64_t layout, int64_t hq, int64_t hkv, int64_t dh);
+at::Tensor decode_gemm_glu(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K,
+                           bool gelu);
+at::Tensor decode_gemm_rope_append(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
+                                   int64_t K, at::Tensor cos, at::Tensor sin,
+                                   at::Tensor positions, at::Tensor k_cache,
+                                   at::Tensor v_cache, at::Tensor slot_mapping,
+                                   int64_t hq);
+at::Tensor decode_swizzle_w_layout(at::Tensor w, int64_t layout, int64_t hq, int64_t hkv,
+                                   int64_t dh);
 at::Tensor lora_delta_(at::Tensor y, at::Tensor t, at::Tensor w, double scale, bool w_transposed);
 at::Tensor lora_badd_(at::Tensor y, at::Tensor t, at::Tensor w, double scale);
 std::vector<at::Tensor> swiglu_packed_dec(at::Tensor y);
@@ -53,7 +63,8 @@ at::Tensor mfma_probe_32x32x16(at::Tensor a, at::Tensor b);
 at::Tensor mfma_probe_16x16x32(at::Tensor a, at::Tensor b);
 at::Tensor train_gemm_nt(at::Tensor a, at::Tensor b);
 at::Tensor skinny_gemm(at::Tensor x, at::Tensor w);
-at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K, int64_t force_split);
+at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K, int64_t force_split,
+                       int64_t layout, int64_t hq, int64_t hkv, int64_t dh);
 at::Tensor decode_swizzle_w(at::Tensor w);
 at::Tensor decode_swizzle_x(at::Tensor x);
 int64_t decode_gemm_split(int64_t N, int64_t K);
@@ -82,7 +93,23 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_res_slab_fwd_dec", &rmsnorm_res_slab_fwd_dec,
         "split-K slab combine + residual + RMSNorm + swizzle in one pass");
   m.def("decode_gemm_raw", &decode_gemm_raw,
-        "decode GEMM returning the uncombined fp32 slab at split>1");
+        "decode GEMM returning the uncombined fp32 slab at split>1",
+        py::arg("xs"), py::arg("ws"), py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("layout") = 0, py::arg("hq") = 0,
+        py::arg("hkv") = 0, py::arg("dh") = 0);
+  m.def("decode_gemm_glu", &decode_gemm_glu,
+        "gate-up decode GEMM (glu16 weight) + fused SwiGLU/GeGLU epilogue "
+        "-> down-proj decode operand",
+        py::arg("xs"), py::arg("ws"), py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("gelu") = false);
+  m.def("decode_gemm_rope_append", &decode_gemm_rope_append,
+        "qkv decode GEMM (rope16 weight) + fused RoPE and paged KV append "
+        "-> rope'd q");
+  m.def("decode_swizzle_w_layout", &decode_swizzle_w_layout,
+        "one-time [N,K] -> row-permuted fragment-lane-major weight layout "
+        "(0 plain, 1 glu16, 2 rope16)",
+        py::arg("w"), py::arg("layout"), py::arg("hq") = 0,
+        py::arg("hkv") = 0, py::arg("dh") = 0);
   m.def("lora_delta_", &lora_delta_,
         "in-place y += scale * t[T,r<=32] @ W[N,r]^T (LoRA merge)");
   m.def("lora_badd_", &lora_badd_,
@@ -130,7 +157,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "v2 weight-stream decode GEMM over pre-swizzled operands: "
         "y[M<=32,N] = x @ W^T (bf16), 1KiB coalesced nt weight bursts",
         py::arg("xs"), py::arg("ws"), py::arg("M"), py::arg("N"),
-        py::arg("K"), py::arg("force_split") = -1);
+        py::arg("K"), py::arg("force_split") = -1, py::arg("layout") = 0,
+        py::arg("hq") = 0, py::arg("hkv") = 0, py::arg("dh") = 0);
   m.def("decode_swizzle_w", &decode_swizzle_w,
         "one-time [N,K] -> fragment-lane-major weight layout");
   m.def("decode_swizzle_x", &decode_swizzle_x,

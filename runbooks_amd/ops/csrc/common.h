@@ -133,6 +133,35 @@ RB_DEV void store_scalar(uint16_t *p, float f) { *p = f32_to_bf16(f); }
 RB_DEV void store_scalar(float *p, float f) { *p = f; }
 
 // ---------------------------------------------------------------------------
+// Epilogue expressions shared by the standalone packed kernels
+// (qkv_fused.hip) and the fused decode-GEMM epilogues (decode_gemm.hip).
+// One definition each, with the fused multiply-adds written out, so both
+// paths round identically whatever the surrounding code looks like.
+// ---------------------------------------------------------------------------
+RB_DEV float silu_mul(float g, float u) {
+  const float s = g / (1.0f + __expf(-g));
+  return s * u;
+}
+
+// tanh approximation (HF gelu_pytorch_tanh)
+RB_DEV float gelu_tanh_mul(float x, float u) {
+  const float p = __builtin_fmaf(0.044715f * x * x, x, x);
+  const float t = tanhf(0.7978845608028654f * p);
+  return 0.5f * x * (1.0f + t) * u;
+}
+
+// rotate-half pair: (a, b) = (x[d], x[d + Dh/2]). The products that are
+// rounded on their own are b*s and b*c; a*c and a*s go into the fused
+// multiply-add unrounded. This is the contraction the compiler chose for
+// `a*c - b*s` / `b*c + a*s` in the standalone kernels before the
+// expression was shared, so their results are unchanged.
+RB_DEV void rope_rot(float a, float b, float c, float s, float &o1,
+                     float &o2) {
+  o1 = __builtin_fmaf(a, c, -(b * s));
+  o2 = __builtin_fmaf(a, s, b * c);
+}
+
+// ---------------------------------------------------------------------------
 // Wave-level reductions (64 lanes).
 // ---------------------------------------------------------------------------
 RB_DEV float wave_reduce_sum(float x) {

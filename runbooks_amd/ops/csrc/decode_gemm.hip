@@ -64,6 +64,54 @@ __device__ __forceinline__ bf16x8v load8v(const uint16_t *p) {
   return c.v;
 }
 
+// ---- weight layout tags and epilogue modes -----------------------------
+// The swizzled weight copy may hold its rows PERMUTED so that the values
+// an elementwise consumer pairs up land in one workgroup's 32-row block:
+//   LAYOUT_GLU16  fused gate-up [2I, K]: block b = gate rows 16b..16b+15
+//                 (local rows 0..15) + up rows 16b..16b+15 (16..31).
+//   LAYOUT_ROPE16 fused qkv: inside each q/k head, block j of the head =
+//                 rows d = 16j..16j+15 (local 0..15) + their rotate-half
+//                 partners d + Dh/2 (local 16..31); v heads in order.
+// A row permutation leaves every output's k-order and the 4-way LDS
+// reduce order alone, so each sum is bit-identical to the plain layout.
+// EPI_*_STORE write y row-major at the ORIGINAL column (4 consecutive
+// local rows stay 4 consecutive columns); the fused modes consume the
+// block in place of swiglu/geglu_packed_dec and qkv_rope_append.
+enum { LAYOUT_PLAIN = 0, LAYOUT_GLU16 = 1, LAYOUT_ROPE16 = 2 };
+enum { EPI_PLAIN = 0, EPI_GLU_STORE, EPI_ROPE_STORE, EPI_SWIGLU, EPI_GEGLU,
+       EPI_ROPE, EPI_ROPE_VT };
+
+struct EpiArgs {
+  int inter;                   // glu16: I
+  int hq, hkv, dh, bs;         // rope16: heads, head dim, cache block size
+  uint16_t *swz;               // glu: down-proj operand [I/16][64][8]
+  uint16_t *q_out;             // rope: [M, Hq, Dh]
+  uint16_t *k_cache, *v_cache;
+  const float *cs, *sn;        // [max_pos, Dh/2] f32
+  const int32_t *pos, *slots;  // [M]
+};
+
+// original y column of local row `en` (a multiple of 4) of block nblk
+template <int EPI>
+__device__ __forceinline__ int epi_col(int nblk, int en, const EpiArgs &e) {
+  if constexpr (EPI == EPI_GLU_STORE) {
+    return (en < 16 ? 0 : e.inter - 16) + nblk * 16 + en;
+  } else if constexpr (EPI == EPI_ROPE_STORE) {
+    const int bph = e.dh / 32;
+    const int head = nblk / bph;
+    if (head >= e.hq + e.hkv) return nblk * 32 + en;
+    const int j = nblk - head * bph;
+    return head * e.dh + 16 * j + (en & 15) + (en < 16 ? 0 : e.dh / 2);
+  } else {
+    return nblk * 32 + en;
+  }
+}
+
+// the 4-wave sum, rounded to bf16 exactly as the y store rounds it
+#define RB_RED_BF16(ROW, M_)                                           \
+  rb::f32_to_bf16(red[0][ROW][M_] + red[1][ROW][M_] + red[2][ROW][M_] + \
+                  red[3][ROW][M_])
+
 // One chunk of U k-steps. W nontemporal (streamed once, must not evict
 // L2); x plain (re-read by every n-block: L2 is exactly where it wants
 // to live). Both streams are lane*16B contiguous per instruction.
@@ -83,11 +131,11 @@ __device__ __forceinline__ bf16x8v load8v(const uint16_t *p) {
 // fp32 slab slice at slabs + kslice*M*N for decode_gemm_combine.
 // U = k-steps (of 16) per unrolled chunk: 8 keeps 3 waves/SIMD, 12
 // trades occupancy (2/SIMD) for a deeper in-flight ring (RB_DG_U=12).
-template <bool STORE_BF16, int U = 8>
+template <bool STORE_BF16, int U = 8, int EPI = EPI_PLAIN>
 __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
     const uint16_t *__restrict__ xs, const uint16_t *__restrict__ ws,
     uint16_t *__restrict__ yp, float *__restrict__ slabs,
-    int M, int N, int K) {
+    int M, int N, int K, const EpiArgs ep) {
   const int tid = threadIdx.x;
   const int wid = tid >> 6;
   const int lane = tid & 63;
@@ -109,6 +157,25 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
   const int s1 = min(steps_total, s0 + spg);
 
   const uint16_t *wseg = ws + (int64_t)nblk * steps_total * 512;
+
+  // rope16 epilogue operands (slot, cos/sin of this thread's two pairs)
+  // depend on nothing the GEMM computes: issue their loads now, so the
+  // pos -> table dependent-load chain hides under the weight stream
+  // instead of sitting on every workgroup's tail.
+  int rp_slot = 0;
+  float2 rp_c = make_float2(0.0f, 0.0f), rp_s = rp_c;
+  if constexpr (EPI == EPI_ROPE || EPI == EPI_ROPE_VT) {
+    const int em = tid >> 3;
+    if (em < M) {
+      rp_slot = ep.slots[em];
+      if (nblk / (ep.dh / 32) < ep.hq + ep.hkv) {
+        const int64_t toff = (int64_t)ep.pos[em] * (ep.dh / 2) +
+                             16 * (nblk % (ep.dh / 32)) + (tid & 7) * 2;
+        rp_c = *reinterpret_cast<const float2 *>(ep.cs + toff);
+        rp_s = *reinterpret_cast<const float2 *>(ep.sn + toff);
+      }
+    }
+  }
 
   f32x16v acc = (f32x16v)(0.0f);
 
@@ -141,6 +208,84 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
   }
   __syncthreads();
 
+  if constexpr (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) {
+    // glu16 block -> k-step nblk of the down-proj operand: wave 0 writes
+    // the 1 KiB chunk [lane = hi*32 + m][8], act(gate) * up of columns
+    // 16*nblk + hi*8 + i. Rows m >= M stay unwritten (dropped downstream).
+    const int m = tid & 31;
+    if (tid < 64 && m < M) {
+      const int r0 = (tid >> 5) * 8;
+      union { uint16_t u[8]; u32x4v q; } o;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float gv = rb::bf16_to_f32(RB_RED_BF16(r0 + i, m));
+        const float uv = rb::bf16_to_f32(RB_RED_BF16(16 + r0 + i, m));
+        o.u[i] = rb::f32_to_bf16(EPI == EPI_GEGLU ? rb::gelu_tanh_mul(gv, uv)
+                                                  : rb::silu_mul(gv, uv));
+      }
+      *reinterpret_cast<u32x4v *>(ep.swz + (int64_t)nblk * 512 + tid * 8) =
+          o.q;
+    }
+    return;
+  } else if constexpr (EPI == EPI_ROPE || EPI == EPI_ROPE_VT) {
+    // rope16 block: uniformly a q, k or v block (head = nblk*32/Dh).
+    const int em = tid >> 3;             // 0..31
+    const int sub = tid & 7;
+    if (em >= M) return;
+    const int bph = ep.dh / 32;
+    const int head = nblk / bph;
+    const int j = nblk - head * bph;
+    if (head < ep.hq + ep.hkv) {         // ---- q / k: 2 rotate-half pairs
+      const int half = ep.dh / 2;
+      const int p = sub * 2;
+      const int d = 16 * j + p;
+      uint16_t *dst;
+      if (head < ep.hq) {
+        dst = ep.q_out + ((int64_t)em * ep.hq + head) * ep.dh + d;
+      } else {
+        const int slot = rp_slot;
+        if (slot < 0) return;
+        dst = ep.k_cache +
+              ((((int64_t)(slot / ep.bs) * ep.hkv + (head - ep.hq)) * ep.bs +
+                slot % ep.bs) * ep.dh) + d;
+      }
+      const float2 c = rp_c, sn = rp_s;
+      const float a0 = rb::bf16_to_f32(RB_RED_BF16(p, em));
+      const float a1 = rb::bf16_to_f32(RB_RED_BF16(p + 1, em));
+      const float b0 = rb::bf16_to_f32(RB_RED_BF16(16 + p, em));
+      const float b1 = rb::bf16_to_f32(RB_RED_BF16(17 + p, em));
+      float x0, y0, x1, y1;
+      rb::rope_rot(a0, b0, c.x, sn.x, x0, y0);
+      rb::rope_rot(a1, b1, c.y, sn.y, x1, y1);
+      *reinterpret_cast<uint32_t *>(dst) =
+          (uint32_t)rb::f32_to_bf16(x0) | ((uint32_t)rb::f32_to_bf16(x1) << 16);
+      *reinterpret_cast<uint32_t *>(dst + half) =
+          (uint32_t)rb::f32_to_bf16(y0) | ((uint32_t)rb::f32_to_bf16(y1) << 16);
+    } else {                             // ---- v: copy into the cache
+      const int slot = rp_slot;
+      if (slot < 0) return;
+      const int hv = head - ep.hq - ep.hkv;
+      const int en = sub * 4;
+      const int d = 32 * j + en;
+      union { uint16_t u[4]; uint64_t q; } o;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o.u[i] = RB_RED_BF16(en + i, em);
+      if constexpr (EPI == EPI_ROPE_VT) {
+        const int64_t vbase =
+            ((int64_t)(slot / ep.bs) * ep.hkv + hv) * (int64_t)ep.dh * ep.bs;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          ep.v_cache[vbase + (int64_t)(d + i) * ep.bs + slot % ep.bs] = o.u[i];
+      } else {
+        *reinterpret_cast<uint64_t *>(
+            ep.v_cache +
+            ((((int64_t)(slot / ep.bs) * ep.hkv + hv) * ep.bs + slot % ep.bs) *
+             ep.dh) + d) = o.q;
+      }
+    }
+    return;
+  }
+
   // 1024 outputs, 4 per thread, n fastest so bf16 stores coalesce 8 B.
   const int em = tid >> 3;               // 0..31
   const int en = (tid & 7) * 4;          // 0,4,..,28
@@ -156,9 +301,10 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) o.u[j] = rb::f32_to_bf16(sum[j]);
       *reinterpret_cast<uint64_t *>(
-          yp + (int64_t)em * N + nblk * 32 + en) = o.q;
+          yp + (int64_t)em * N + epi_col<EPI>(nblk, en, ep)) = o.q;
     } else {
-      float *slab = slabs + ((int64_t)kslice * M + em) * N + nblk * 32 + en;
+      float *slab = slabs + ((int64_t)kslice * M + em) * N +
+                    epi_col<EPI>(nblk, en, ep);
       *reinterpret_cast<float4 *>(slab) =
           make_float4(sum[0], sum[1], sum[2], sum[3]);
     }
@@ -263,10 +409,6 @@ at::Tensor decode_swizzle_x(at::Tensor x) {
   return xs;
 }
 
-// Raw variant for fused consumers: split == 1 returns y bf16 [M, N];
-// split > 1 returns the fp32 slab [split, M, N] UNCOMBINED — the
-// consumer kernel (rmsnorm_res_slab_fwd_dec) folds the slices while it
-// reads, saving the combine launch inside the decode graph.
 static int dg_u() {
   static int u = [] {
     const char *e = getenv("RB_DG_U");
@@ -275,53 +417,126 @@ static int dg_u() {
   return u;
 }
 
-at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M,
-                           int64_t N, int64_t K) {
+namespace {
+
+template <bool STORE_BF16, int EPI>
+void launch_dg(int u, int split, hipStream_t stream, const at::Tensor &xs,
+               const at::Tensor &ws, uint16_t *y, float *slabs, int64_t M,
+               int64_t N, int64_t K, const EpiArgs &ep) {
+  const dim3 grid(N / 32, split);
+  if (u == 12)
+    hipLaunchKernelGGL((decode_gemm_kernel<STORE_BF16, 12, EPI>), grid,
+                       dim3(BLOCK), 0, stream,
+                       (const uint16_t *)xs.data_ptr(),
+                       (const uint16_t *)ws.data_ptr(), y, slabs,
+                       (int)M, (int)N, (int)K, ep);
+  else
+    hipLaunchKernelGGL((decode_gemm_kernel<STORE_BF16, 8, EPI>), grid,
+                       dim3(BLOCK), 0, stream,
+                       (const uint16_t *)xs.data_ptr(),
+                       (const uint16_t *)ws.data_ptr(), y, slabs,
+                       (int)M, (int)N, (int)K, ep);
+}
+
+// un-permuting (or plain) store, by layout tag
+template <bool STORE_BF16>
+void launch_dg_store(int64_t layout, int u, int split, hipStream_t stream,
+                     const at::Tensor &xs, const at::Tensor &ws, uint16_t *y,
+                     float *slabs, int64_t M, int64_t N, int64_t K,
+                     const EpiArgs &ep) {
+  if (layout == LAYOUT_GLU16)
+    launch_dg<STORE_BF16, EPI_GLU_STORE>(u, split, stream, xs, ws, y, slabs,
+                                         M, N, K, ep);
+  else if (layout == LAYOUT_ROPE16)
+    launch_dg<STORE_BF16, EPI_ROPE_STORE>(u, split, stream, xs, ws, y, slabs,
+                                          M, N, K, ep);
+  else
+    launch_dg<STORE_BF16, EPI_PLAIN>(u, split, stream, xs, ws, y, slabs,
+                                     M, N, K, ep);
+}
+
+EpiArgs layout_args(int64_t layout, int64_t N, int64_t hq, int64_t hkv,
+                    int64_t dh) {
+  EpiArgs ep = {};
+  TORCH_CHECK(layout >= LAYOUT_PLAIN && layout <= LAYOUT_ROPE16,
+              "decode_gemm: unknown weight layout ", layout);
+  if (layout == LAYOUT_GLU16) {
+    TORCH_CHECK(N % 32 == 0, "decode_gemm: glu16 needs I % 16 == 0");
+    ep.inter = (int)(N / 2);
+  } else if (layout == LAYOUT_ROPE16) {
+    TORCH_CHECK(dh > 0 && dh % 32 == 0 && (hq + 2 * hkv) * dh == N,
+                "decode_gemm: rope16 needs (Dh/2) % 16 == 0 and "
+                "N == (Hq + 2*Hkv) * Dh");
+    ep.hq = (int)hq; ep.hkv = (int)hkv; ep.dh = (int)dh;
+  }
+  return ep;
+}
+
+void check_operands(const at::Tensor &xs, const at::Tensor &ws, int64_t M,
+                    int64_t N, int64_t K, const char *who) {
   TORCH_CHECK(xs.is_cuda() && ws.is_cuda() && xs.is_contiguous() &&
               ws.is_contiguous() && xs.scalar_type() == at::kBFloat16 &&
-              ws.scalar_type() == at::kBFloat16, "decode_gemm_raw: inputs");
+              ws.scalar_type() == at::kBFloat16, who, ": inputs");
   TORCH_CHECK(xs.numel() == (K / 16) * 512 && ws.numel() == N * K &&
-              decode_gemm_supported(M, N, K), "decode_gemm_raw: shape");
+              decode_gemm_supported(M, N, K), who, ": shape");
+}
+
+}  // namespace
+
+// One-time permuted weight swizzle for a layout tag: row r of the
+// permuted matrix is row perm[r] of w, built from the same block rules
+// the kernel's epilogues invert (LAYOUT_* above).
+at::Tensor decode_swizzle_w_layout(at::Tensor w, int64_t layout, int64_t hq,
+                                   int64_t hkv, int64_t dh) {
+  TORCH_CHECK(w.dim() == 2, "decode_swizzle_w_layout: [N,K]");
+  const int64_t N = w.size(0);
+  layout_args(layout, N, hq, hkv, dh);
+  if (layout == LAYOUT_PLAIN) return decode_swizzle_w(w);
+  auto perm = at::empty({N}, at::TensorOptions().dtype(at::kLong));
+  int64_t *p = perm.data_ptr<int64_t>();
+  for (int64_t r = 0; r < N; ++r) {
+    const int64_t b = r / 32, l = r % 32;
+    if (layout == LAYOUT_GLU16) {
+      p[r] = (l < 16 ? 0 : N / 2 - 16) + 16 * b + l;
+    } else {
+      const int64_t bph = dh / 32, head = b / bph, j = b % bph;
+      p[r] = head >= hq + hkv
+                 ? r
+                 : head * dh + 16 * j + (l & 15) + (l < 16 ? 0 : dh / 2);
+    }
+  }
+  return decode_swizzle_w(w.index_select(0, perm.to(w.device())));
+}
+
+// Raw variant for fused consumers: split == 1 returns y bf16 [M, N];
+// split > 1 returns the fp32 slab [split, M, N] UNCOMBINED — the
+// consumer kernel (rmsnorm_res_slab_fwd_dec) folds the slices while it
+// reads, saving the combine launch inside the decode graph.
+at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M,
+                           int64_t N, int64_t K, int64_t layout, int64_t hq,
+                           int64_t hkv, int64_t dh) {
+  check_operands(xs, ws, M, N, K, "decode_gemm_raw");
+  const EpiArgs ep = layout_args(layout, N, hq, hkv, dh);
   auto stream = at::cuda::getCurrentHIPStream();
   const int split = (int)decode_gemm_split(N, K);
   if (split == 1) {
     auto y = at::empty({M, N}, xs.options());
-    if (dg_u() == 12)
-      hipLaunchKernelGGL((decode_gemm_kernel<true, 12>), dim3(N / 32, 1),
-                         dim3(BLOCK), 0, stream,
-                         (const uint16_t *)xs.data_ptr(),
-                         (const uint16_t *)ws.data_ptr(),
-                         (uint16_t *)y.data_ptr(), nullptr,
-                         (int)M, (int)N, (int)K);
-    else
-      hipLaunchKernelGGL((decode_gemm_kernel<true, 8>), dim3(N / 32, 1),
-                         dim3(BLOCK), 0, stream,
-                         (const uint16_t *)xs.data_ptr(),
-                         (const uint16_t *)ws.data_ptr(),
-                         (uint16_t *)y.data_ptr(), nullptr,
-                         (int)M, (int)N, (int)K);
+    launch_dg_store<true>(layout, dg_u(), 1, stream, xs, ws,
+                          (uint16_t *)y.data_ptr(), nullptr, M, N, K, ep);
     return y;
   }
   auto slabs = at::empty({split, M, N}, xs.options().dtype(at::kFloat));
-  if (dg_u() == 12)
-    hipLaunchKernelGGL((decode_gemm_kernel<false, 12>), dim3(N / 32, split),
-                       dim3(BLOCK), 0, stream,
-                       (const uint16_t *)xs.data_ptr(),
-                       (const uint16_t *)ws.data_ptr(), nullptr,
-                       (float *)slabs.data_ptr(), (int)M, (int)N, (int)K);
-  else
-    hipLaunchKernelGGL((decode_gemm_kernel<false, 8>), dim3(N / 32, split),
-                       dim3(BLOCK), 0, stream,
-                       (const uint16_t *)xs.data_ptr(),
-                       (const uint16_t *)ws.data_ptr(), nullptr,
-                       (float *)slabs.data_ptr(), (int)M, (int)N, (int)K);
+  launch_dg_store<false>(layout, dg_u(), split, stream, xs, ws, nullptr,
+                         (float *)slabs.data_ptr(), M, N, K, ep);
   return slabs;
 }
 
-// xs from decode_swizzle_x, ws from decode_swizzle_w; M/N/K of the
-// ORIGINAL y[M,N] = x[M,K] @ W[N,K]^T problem.
+// xs from decode_swizzle_x, ws from decode_swizzle_w(_layout); M/N/K of
+// the ORIGINAL y[M,N] = x[M,K] @ W[N,K]^T problem. y is row-major in the
+// original column order whatever the weight layout.
 at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
-                       int64_t K, int64_t force_split) {
+                       int64_t K, int64_t force_split, int64_t layout,
+                       int64_t hq, int64_t hkv, int64_t dh) {
   TORCH_CHECK(xs.is_cuda() && ws.is_cuda() && xs.is_contiguous() &&
               ws.is_contiguous(), "decode_gemm: contiguous GPU tensors");
   TORCH_CHECK(xs.scalar_type() == at::kBFloat16 &&
@@ -330,25 +545,19 @@ at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
   TORCH_CHECK(ws.numel() == N * K, "decode_gemm: ws size");
   TORCH_CHECK(decode_gemm_supported(M, N, K),
               "decode_gemm: unsupported shape ", M, "x", N, "x", K);
+  const EpiArgs ep = layout_args(layout, N, hq, hkv, dh);
 
   auto stream = at::cuda::getCurrentHIPStream();
   auto y = at::empty({M, N}, xs.options());
   const int split = force_split > 0 ? (int)force_split
                                     : (int)decode_gemm_split(N, K);
   if (split == 1) {
-    hipLaunchKernelGGL((decode_gemm_kernel<true>), dim3(N / 32, 1),
-                       dim3(BLOCK), 0, stream,
-                       (const uint16_t *)xs.data_ptr(),
-                       (const uint16_t *)ws.data_ptr(),
-                       (uint16_t *)y.data_ptr(), nullptr,
-                       (int)M, (int)N, (int)K);
+    launch_dg_store<true>(layout, 8, 1, stream, xs, ws,
+                          (uint16_t *)y.data_ptr(), nullptr, M, N, K, ep);
   } else {
     auto slabs = at::empty({split, M, N}, xs.options().dtype(at::kFloat));
-    hipLaunchKernelGGL((decode_gemm_kernel<false>), dim3(N / 32, split),
-                       dim3(BLOCK), 0, stream,
-                       (const uint16_t *)xs.data_ptr(),
-                       (const uint16_t *)ws.data_ptr(), nullptr,
-                       (float *)slabs.data_ptr(), (int)M, (int)N, (int)K);
+    launch_dg_store<false>(layout, 8, split, stream, xs, ws, nullptr,
+                           (float *)slabs.data_ptr(), M, N, K, ep);
     const int64_t mn = M * N;
     const int grid = rb::rb_grid_1d(mn / 4, 256);
     hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3(grid), dim3(256),
@@ -356,4 +565,81 @@ at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
                        (uint16_t *)y.data_ptr(), split, mn);
   }
   return y;
+}
+
+// Gate-up decode GEMM on a glu16 weight with the activation fused into
+// the epilogue: returns the down-proj operand ([I/16][64][8] bf16, the
+// layout decode_swizzle_x builds) of act(x Wg^T) * (x Wu^T). Values are
+// those of swiglu/geglu_packed_dec(decode_gemm(...)); the row-major
+// [M, I] tensor is not produced.
+at::Tensor decode_gemm_glu(at::Tensor xs, at::Tensor ws, int64_t M,
+                           int64_t N, int64_t K, bool gelu) {
+  check_operands(xs, ws, M, N, K, "decode_gemm_glu");
+  TORCH_CHECK(decode_gemm_split(N, K) == 1,
+              "decode_gemm_glu: fused epilogue needs split == 1");
+  EpiArgs ep = layout_args(LAYOUT_GLU16, N, 0, 0, 0);
+  auto swz = at::empty({(N / 32) * 512}, xs.options());
+  ep.swz = (uint16_t *)swz.data_ptr();
+  auto stream = at::cuda::getCurrentHIPStream();
+  if (gelu)
+    launch_dg<true, EPI_GEGLU>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
+                               M, N, K, ep);
+  else
+    launch_dg<true, EPI_SWIGLU>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
+                                M, N, K, ep);
+  return swz;
+}
+
+// qkv decode GEMM on a rope16 weight with RoPE + KV append fused into
+// the epilogue: returns RoPE'd q [M, Hq, Dh]; RoPE'd k and plain v go
+// straight into the paged bf16 cache (rows with slot < 0 skipped). Same
+// values and cache layouts as qkv_rope_append(decode_gemm(...)).
+at::Tensor decode_gemm_rope_append(at::Tensor xs, at::Tensor ws, int64_t M,
+                                   int64_t N, int64_t K, at::Tensor cos,
+                                   at::Tensor sin, at::Tensor positions,
+                                   at::Tensor k_cache, at::Tensor v_cache,
+                                   at::Tensor slot_mapping, int64_t hq) {
+  check_operands(xs, ws, M, N, K, "decode_gemm_rope_append");
+  TORCH_CHECK(decode_gemm_split(N, K) == 1,
+              "decode_gemm_rope_append: fused epilogue needs split == 1");
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() && k_cache.dim() == 4 &&
+              v_cache.dim() == 4 && k_cache.is_contiguous() &&
+              v_cache.is_contiguous() &&
+              k_cache.scalar_type() == at::kBFloat16 &&
+              v_cache.scalar_type() == at::kBFloat16 &&
+              v_cache.numel() == k_cache.numel(),
+              "decode_gemm_rope_append: bf16 paged cache");
+  const int64_t hkv = k_cache.size(1), bs = k_cache.size(2),
+                dh = k_cache.size(3);
+  EpiArgs ep = layout_args(LAYOUT_ROPE16, N, hq, hkv, dh);
+  TORCH_CHECK(positions.is_cuda() && slot_mapping.is_cuda() &&
+              positions.scalar_type() == at::kInt &&
+              slot_mapping.scalar_type() == at::kInt &&
+              positions.is_contiguous() && slot_mapping.is_contiguous() &&
+              positions.numel() >= M && slot_mapping.numel() >= M,
+              "decode_gemm_rope_append: idx");
+  TORCH_CHECK(cos.is_cuda() && sin.is_cuda() &&
+              cos.scalar_type() == at::kFloat &&
+              sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+              sin.is_contiguous() && cos.dim() == 2 &&
+              cos.size(1) == dh / 2 && sin.sizes() == cos.sizes(),
+              "decode_gemm_rope_append: rope tables [P, Dh/2] f32");
+  auto q = at::empty({M, hq, dh}, xs.options());
+  ep.bs = (int)bs;
+  ep.q_out = (uint16_t *)q.data_ptr();
+  ep.k_cache = (uint16_t *)k_cache.data_ptr();
+  ep.v_cache = (uint16_t *)v_cache.data_ptr();
+  ep.cs = cos.data_ptr<float>();
+  ep.sn = sin.data_ptr<float>();
+  ep.pos = positions.data_ptr<int32_t>();
+  ep.slots = slot_mapping.data_ptr<int32_t>();
+  const bool vt = v_cache.size(2) == dh && v_cache.size(3) == bs && dh != bs;
+  auto stream = at::cuda::getCurrentHIPStream();
+  if (vt)
+    launch_dg<true, EPI_ROPE_VT>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
+                                 M, N, K, ep);
+  else
+    launch_dg<true, EPI_ROPE>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
+                              M, N, K, ep);
+  return q;
 }

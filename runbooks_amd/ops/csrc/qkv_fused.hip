@@ -29,8 +29,10 @@ __device__ __forceinline__ void rope_pair(
   for (int k = 0; k < n; ++k) {
     const float a = rb::bf16_to_f32(src1[k]);
     const float b = rb::bf16_to_f32(src2[k]);
-    dst1[k] = rb::f32_to_bf16(a * c[k] - b * s[k]);
-    dst2[k] = rb::f32_to_bf16(b * c[k] + a * s[k]);
+    float o1, o2;
+    rb::rope_rot(a, b, c[k], s[k], o1, o2);
+    dst1[k] = rb::f32_to_bf16(o1);
+    dst2[k] = rb::f32_to_bf16(o2);
   }
 }
 
@@ -125,10 +127,7 @@ __global__ void swiglu_packed_kernel(const T *__restrict__ y,
     rb::VIO<T>::load(y + (row * 2 * inter) + v * W, g);
     rb::VIO<T>::load(y + (row * 2 * inter) + inter + v * W, u);
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-      const float s = g[k] / (1.0f + __expf(-g[k]));
-      g[k] = s * u[k];
-    }
+    for (int k = 0; k < W; ++k) g[k] = rb::silu_mul(g[k], u[k]);
     rb::VIO<T>::store(out + row * inter + v * W, g);
     if constexpr (sizeof(T) == 2) {
       if (swz != nullptr) {
@@ -161,12 +160,7 @@ __global__ void geglu_packed_kernel(const T *__restrict__ y,
     rb::VIO<T>::load(y + (row * 2 * inter) + v * W, g);
     rb::VIO<T>::load(y + (row * 2 * inter) + inter + v * W, u);
 #pragma unroll
-    for (int k = 0; k < W; ++k) {
-      // tanh approximation (HF gelu_pytorch_tanh)
-      const float x = g[k];
-      const float t = tanhf(0.7978845608028654f * (x + 0.044715f * x * x * x));
-      g[k] = 0.5f * x * (1.0f + t) * u[k];
-    }
+    for (int k = 0; k < W; ++k) g[k] = rb::gelu_tanh_mul(g[k], u[k]);
     rb::VIO<T>::store(out + row * inter + v * W, g);
     if constexpr (sizeof(T) == 2) {
       if (swz != nullptr) {

@@ -31,11 +31,28 @@ _FP8_REGISTRY: dict[int, tuple[torch.Tensor, torch.Tensor]] = {}
 # consumed by csrc/decode_gemm.hip. A second full-precision weight copy:
 # 288 GB HBM3E per GPU makes layout-specialized decode weights the right
 # trade on MI355X (prefill/training keep the original [N,K] tensor).
-# value: (swizzled copy, (N, K), weakref to the registered tensor).
+# value: (swizzled copy, (N, K), layout, weakref to the registered tensor).
 # data_ptr alone is NOT a safe key — a freed weight's address gets
 # recycled by later allocations, so every lookup verifies tensor
 # identity through the weakref (stale entries are dropped lazily).
+#
+# layout = (tag, hq, hkv, dh) names the ROW ORDER of the swizzled copy
+# (csrc/decode_gemm.hip LAYOUT_*): "plain"; "glu16" (fused gate-up: each
+# 32-row block = 16 gate rows + the matching 16 up rows); "rope16" (fused
+# qkv: each q/k block = 16 rows d + their rotate-half partners d + Dh/2).
+# The permuted layouts let the GEMM epilogue apply SwiGLU/GeGLU or
+# RoPE + KV append in place; every other caller gets y in the original
+# column order through the kernel's un-permuting store. Only the swizzled
+# copy is permuted — the [N, K] master is untouched.
 _DECODE_W_REGISTRY: dict[int, tuple] = {}
+
+_LAYOUT_ID = {"plain": 0, "glu16": 1, "rope16": 2}
+
+
+def fused_epilogue_enabled() -> bool:
+    """RB_FUSED_EPILOGUE=0 keeps the separate swiglu / qkv_rope_append
+    kernels behind the decode GEMMs (A/B switch and test reference)."""
+    return os.environ.get("RB_FUSED_EPILOGUE", "1") == "1"
 
 
 def _registry_get(reg: dict, weight: torch.Tensor):
@@ -48,13 +65,21 @@ def _registry_get(reg: dict, weight: torch.Tensor):
     return entry
 
 
-def register_decode_weight(weight: torch.Tensor) -> None:
-    """Build + register the decode-GEMM weight layout for `weight`."""
+def register_decode_weight(weight: torch.Tensor, layout: str = "plain",
+                           hq: int = 0, hkv: int = 0, dh: int = 0) -> None:
+    """Build + register the decode-GEMM weight layout for `weight`.
+    `layout` "glu16" needs a fused gate-up [2I, K] with I % 16 == 0;
+    "rope16" a fused qkv [(hq + 2*hkv) * dh, K] with (dh/2) % 16 == 0."""
     for ptr in [p for p, e in _DECODE_W_REGISTRY.items() if e[-1]() is None]:
         del _DECODE_W_REGISTRY[ptr]          # purge dead entries
-    ws = _backend.ext().decode_swizzle_w(weight.data)
+    if layout == "rope16":
+        meta = (layout, int(hq), int(hkv), int(dh))
+    else:
+        meta = (layout, 0, 0, 0)
+    ws = _backend.ext().decode_swizzle_w_layout(
+        weight.data, _LAYOUT_ID[layout], *meta[1:])
     _DECODE_W_REGISTRY[weight.data_ptr()] = (
-        ws, (int(weight.shape[0]), int(weight.shape[1])),
+        ws, (int(weight.shape[0]), int(weight.shape[1])), meta,
         weakref.ref(weight))
 
 E4M3_MAX = 448.0
@@ -190,7 +215,9 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                     if xs is None:
                         xs = _backend.ext().decode_swizzle_x(
                             x.reshape(m, k).contiguous())
-                    y = _backend.ext().decode_gemm(xs, dw[0], m, n, k)
+                    tag, hq, hkv, dh = dw[2]
+                    y = _backend.ext().decode_gemm(
+                        xs, dw[0], m, n, k, -1, _LAYOUT_ID[tag], hq, hkv, dh)
                     return y.view(*x.shape[:-1], n)
             if _USE_SKINNY and n % 64 == 0 and k % 256 == 0:
                 y = _backend.ext().skinny_gemm(x.reshape(m, k).contiguous(),
@@ -199,23 +226,90 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
     return F.linear(x, weight, bias)
 
 
-def decode_linear_raw(x, weight):
+def decode_linear_raw(x, weight, xs=None, m=None):
     """Decode GEMM that may return an UNCOMBINED fp32 split-K slab
     [split, M, N] (consumer kernels fold it — rmsnorm_res_slab_fwd_dec),
     or a plain bf16 [M, N]. Falls back to fast_linear when the weight
-    has no registered decode layout. Returns (out, is_slab)."""
+    has no registered decode layout. Returns (out, is_slab).
+
+    A producer that emits only the pre-swizzled operand (decode_linear_glu)
+    passes it as `xs` with its row count `m` and x=None; the weight must
+    then have a registered decode layout."""
     dw = _registry_get(_DECODE_W_REGISTRY, weight)
     if dw is None or not _USE_DECODE_GEMM:
+        if x is None:
+            raise RuntimeError("decode_linear_raw: operand-only input needs "
+                               "a registered decode weight")
         with torch.no_grad():
             return fast_linear(x, weight), False
-    k = x.shape[-1]
-    m = x.numel() // k
+    k = weight.shape[1]
     n = weight.shape[0]
+    if xs is None:
+        m = x.numel() // k
+        xs = getattr(x, "_rb_swz", None)
+        if xs is None:
+            xs = _backend.ext().decode_swizzle_x(x.reshape(m, k).contiguous())
+    tag, hq, hkv, dh = dw[2]
+    out = _backend.ext().decode_gemm_raw(xs, dw[0], m, n, k,
+                                         _LAYOUT_ID[tag], hq, hkv, dh)
+    return out, out.dtype == torch.float32
+
+
+def decode_layout(weight) -> str | None:
+    """Layout tag of `weight`'s registered decode copy (None: none)."""
+    if not _USE_DECODE_GEMM:
+        return None
+    dw = _registry_get(_DECODE_W_REGISTRY, weight)
+    return None if dw is None else dw[2][0]
+
+
+def fused_epilogue_ok(x, weight, tag: str) -> bool:
+    """True when the decode GEMM of x @ weight^T can run with the fused
+    `tag` epilogue: matching registered layout, m <= 32, bf16, a
+    single-pass (split == 1) GEMM, and RB_FUSED_EPILOGUE on."""
+    if not (fused_epilogue_enabled() and x.dtype == torch.bfloat16
+            and _backend.use_hip(x) and decode_layout(weight) == tag):
+        return False
+    k = x.shape[-1]
+    n = weight.shape[0]
+    ext = _backend.ext()
+    return (x.numel() // k <= 32 and ext.decode_gemm_supported(
+        x.numel() // k, n, k) and ext.decode_gemm_split(n, k) == 1)
+
+
+def _operand(x, m, k):
     xs = getattr(x, "_rb_swz", None)
     if xs is None:
         xs = _backend.ext().decode_swizzle_x(x.reshape(m, k).contiguous())
-    out = _backend.ext().decode_gemm_raw(xs, dw[0], m, n, k)
-    return out, out.dtype == torch.float32
+    return xs
+
+
+def decode_linear_glu(x, weight, gelu: bool = False):
+    """Gate-up decode GEMM with SwiGLU (or GeGLU) fused into its epilogue
+    (fused_epilogue_ok(x, weight, "glu16") must hold). Returns (operand,
+    m): the down-proj decode operand, for decode_linear_raw(xs=, m=)."""
+    dw = _registry_get(_DECODE_W_REGISTRY, weight)
+    k = x.shape[-1]
+    m = x.numel() // k
+    return _backend.ext().decode_gemm_glu(
+        _operand(x, m, k), dw[0], m, weight.shape[0], k, gelu), m
+
+
+def decode_linear_rope_append(x, weight, cos, sin, positions, k_cache,
+                              v_cache, slot_mapping, hq: int):
+    """qkv decode GEMM with RoPE + paged KV append fused into its epilogue
+    (fused_epilogue_ok(x, weight, "rope16") must hold; bf16 cache).
+    Returns RoPE'd q [m, hq, dh]."""
+    dw = _registry_get(_DECODE_W_REGISTRY, weight)
+    if dw[2][1:] != (hq, k_cache.shape[1], k_cache.shape[3]):
+        raise RuntimeError(f"decode_linear_rope_append: weight registered "
+                           f"for heads {dw[2][1:]}, called with "
+                           f"{(hq, k_cache.shape[1], k_cache.shape[3])}")
+    k = x.shape[-1]
+    m = x.numel() // k
+    return _backend.ext().decode_gemm_rope_append(
+        _operand(x, m, k), dw[0], m, weight.shape[0], k, cos, sin,
+        positions, k_cache, v_cache, slot_mapping, hq)
 
 
 class Linear(torch.nn.Linear):
