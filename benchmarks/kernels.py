@@ -124,6 +124,29 @@ def main():
     out.append(row("flash_fwd+bwd", "b4 s512 h32 d128", us,
                    10 * qq.numel() * 2, flops=3.5 * fl))
 
+    # prefill of a 128-token tail behind a 1024-token cached prefix, next to
+    # the dense prefill of the whole 1152 tokens it replaces on a prefix hit
+    CTX, TQ, HP = 1024, 128, 32
+    SP = CTX + TQ
+    qp = torch.randn(1, SP, HP, 128, dtype=bf16, device=dev)
+    kp, vp = torch.randn_like(qp), torch.randn_like(qp)
+    us = timeit(lambda: ops.flash_prefill(qp, kp, vp))
+    out.append(row("flash_prefill", f"b1 s{SP} h{HP} d128", us,
+                   4 * qp.numel() * 2, flops=4 * HP * SP * SP * 128 / 2))
+    nbp = SP // 16
+    btp = torch.randperm(nbp + 8, device=dev)[:nbp].to(torch.int32)
+    slots = (btp.long().repeat_interleave(16) * 16 +
+             torch.arange(SP, device=dev) % 16).to(torch.int32)
+    qt = qp[0, CTX:].contiguous()
+    flp = 4 * HP * 128 * (TQ * CTX + TQ * (TQ + 1) / 2)
+    for vt in (False, True):
+        kcp, vcp = ops.alloc_kv_cache(nbp + 8, HP, 128, dev, v_transposed=vt)
+        ops.kv_append(kp[0], vp[0], kcp, vcp, slots)
+        us = timeit(lambda: ops.paged_prefill(qt, kcp, vcp, btp, CTX))
+        out.append(row("paged_prefill_vt" if vt else "paged_prefill",
+                       f"ctx{CTX} T{TQ} h{HP} d128", us,
+                       (2 * qt.numel() + 2 * SP * HP * 128) * 2, flops=flp))
+
     # paged decode b32 len512
     BS, B, L = 16, 32, 512
     nb = B * (L // BS) + 8

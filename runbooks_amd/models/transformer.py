@@ -8,10 +8,12 @@ One implementation, three family knobs (ModelConfig):
   * parallel_residual: falcon's attn+mlp-in-parallel block
   * GQA/MQA via num_kv_heads (llama2-70b 8, falcon-40b 8, falcon-7b 1)
 
-Three forward modes:
+Forward modes:
   * ``forward(tokens)``             — training, full causal attention
   * ``prefill(...)``                — fills the paged KV cache, returns
                                       last-position logits
+  * ``prefill_paged(...)``          — one chunk of one prompt whose earlier
+                                      positions are already in the cache
   * ``decode(...)``                 — one token per sequence against the
                                       paged cache (gfx950 decode kernel)
 
@@ -114,6 +116,17 @@ class Attention(nn.Module):
         o = ops.flash_prefill(q, k.view(B, S, self.hkv, self.dh),
                               v.view(B, S, self.hkv, self.dh), scale=self.scale)
         return self.o_proj(o.reshape(B * S, self.hq * self.dh))
+
+    def forward_prefill_paged(self, x, cos, sin, positions, kc, vc,
+                              slot_mapping, block_table, ctx_len):
+        """One chunk of one sequence: append its k/v, then attend over the
+        whole cached prefix + chunk through the block table."""
+        T = x.shape[0]
+        q, k, v = self._qkv(x, cos, sin, positions)
+        ops.kv_append(k, v, kc, vc, slot_mapping)
+        o = ops.paged_prefill(q, kc, vc, block_table, ctx_len,
+                              scale=self.scale)
+        return self.o_proj(o.reshape(T, self.hq * self.dh))
 
     def forward_decode(self, x, cos, sin, positions, kc, vc, slot_mapping,
                        block_tables, seq_lens, nsplit=None, slab_ok=False,
@@ -396,6 +409,26 @@ class Transformer(nn.Module):
                 h, self.rope_cos, self.rope_sin, positions, kc, vc, slot_mapping, B, S)
             x = blk(x, fn)
         x = self.norm_f(x.view(B, S, -1)[:, -1])
+        logits = self.lm_head(x)
+        return gather_from_tp(logits) if self._lm_vocab_parallel else logits
+
+    @torch.no_grad()
+    def prefill_paged(self, tokens, positions, caches, slot_mapping,
+                      block_table, ctx_len):
+        """Prefill tokens [1, T] of ONE sequence whose first ``ctx_len``
+        positions are already in the paged cache (prefix-cache hit or an
+        earlier chunk). ``positions`` are absolute ([T], starting at
+        ctx_len); ``block_table`` (int32 [>= ceil((ctx_len+T)/16)]) maps
+        the whole sequence. Returns last-position logits [1, V]."""
+        assert tokens.shape[0] == 1, "prefill_paged takes one sequence"
+        T = tokens.shape[1]
+        x = self._embed(tokens, positions)
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_prefill_paged(  # noqa: E731
+                h, self.rope_cos, self.rope_sin, positions, kc, vc,
+                slot_mapping, block_table, ctx_len)
+            x = blk(x, fn)
+        x = self.norm_f(x.view(1, T, -1)[:, -1])
         logits = self.lm_head(x)
         return gather_from_tp(logits) if self._lm_vocab_parallel else logits
 

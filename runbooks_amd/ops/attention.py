@@ -10,6 +10,10 @@
 * ``paged_decode``: single-token decode against the paged KV cache —
   gfx950 HIP kernel on GPU (csrc/attention_decode.hip), fp32 reference on
   CPU (also the numerics oracle for the GPU test).
+
+* ``paged_prefill``: one chunk of one sequence's prompt attending over the
+  paged KV cache (cached prefix + the chunk itself) — gfx950 MFMA kernel
+  on GPU (csrc/attention_prefill_paged.hip), fp32 reference on CPU.
 """
 from __future__ import annotations
 
@@ -146,6 +150,64 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, seq_lens, scale,
             p = torch.softmax(s, dim=0)
             out[b, h] = (p @ v[:, hk]).to(q.dtype)
     return out
+
+
+def paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale=None):
+    """fp32 reference for paged_prefill: gather keys [0, ctx_len + T) from
+    the cache (plain or transposed-V blocks; fp8 caches are dequantized up
+    front), then masked softmax — row r sees keys <= ctx_len + r.
+    q [T, Hq, Dh] -> [T, Hq, Dh] in q's dtype."""
+    if k_cache.dtype == torch.uint8:
+        from .kvcache import fp8_dequant_cache_ref
+        k_cache = fp8_dequant_cache_ref(k_cache)
+        v_cache = fp8_dequant_cache_ref(v_cache)
+    T, Hq, Dh = q.shape
+    _, Hkv, BS, _ = k_cache.shape
+    if scale is None:
+        scale = 1.0 / math.sqrt(Dh)
+    ctx_len = int(ctx_len)
+    n = ctx_len + T
+    vt = (v_cache.shape[2] == Dh and v_cache.shape[3] == BS and Dh != BS)
+    blocks = block_table[: (n + BS - 1) // BS].long().to(k_cache.device)
+    k = k_cache[blocks].transpose(1, 2).reshape(-1, Hkv, Dh)[:n].float()
+    if vt:
+        v = v_cache[blocks].permute(0, 3, 1, 2).reshape(-1, Hkv, Dh)[:n].float()
+    else:
+        v = v_cache[blocks].transpose(1, 2).reshape(-1, Hkv, Dh)[:n].float()
+    g = Hq // Hkv
+    if g > 1:
+        k = k.repeat_interleave(g, dim=1)
+        v = v.repeat_interleave(g, dim=1)
+    # [Hq, T, n] scores; key j is masked for row r when j > ctx_len + r
+    s = torch.einsum("thd,nhd->htn", q.float(), k) * scale
+    rows = torch.arange(T, device=q.device)[:, None] + ctx_len
+    keys = torch.arange(n, device=q.device)[None, :]
+    s = s.masked_fill(keys > rows, float("-inf"))
+    p = torch.softmax(s, dim=-1)
+    return torch.einsum("htn,nhd->thd", p, v).to(q.dtype)
+
+
+def paged_prefill(q, k_cache, v_cache, block_table, ctx_len,
+                  scale: float | None = None):
+    """Causal attention of one prompt chunk over the paged cache.
+
+    q [T, Hq, Dh]: one sequence, row r at absolute position ctx_len + r.
+    The chunk's own k/v must already be appended, so keys [0, ctx_len + T)
+    are all read through ``block_table`` (int32 [>= ceil((ctx_len+T)/16)]).
+    GPU: bf16 caches in either alloc_kv_cache layout run the gfx950 MFMA
+    kernel; fp8 caches raise. CPU: fp32 reference.
+    """
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _backend.use_hip(q):
+        if k_cache.dtype == torch.uint8:
+            raise NotImplementedError(
+                "paged_prefill: fp8 KV caches are not supported")
+        return _backend.ext().flash_prefill_paged(
+            q.contiguous(), k_cache, v_cache,
+            block_table.to(torch.int32).contiguous(), int(ctx_len),
+            float(scale))
+    return paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale)
 
 
 def _is_vt(k_cache, v_cache) -> bool:

@@ -48,6 +48,8 @@ std::vector<at::Tensor> paged_decode_swz(at::Tensor q, at::Tensor k_cache,
                                          double scale,
                                          c10::optional<at::Tensor> seq_starts);
 at::Tensor flash_prefill(at::Tensor q, at::Tensor k, at::Tensor v, double scale);
+at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
+                               at::Tensor block_table, int64_t ctx_len, double scale);
 std::vector<at::Tensor> flash_fwd_train(at::Tensor q, at::Tensor k, at::Tensor v,
                                         double scale);
 std::vector<at::Tensor> fa_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
@@ -138,6 +140,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("nsplit"),
         py::arg("scale"), py::arg("seq_starts") = py::none());
   m.def("flash_prefill", &flash_prefill, "MFMA flash-attention prefill (causal)");
+  m.def("flash_prefill_paged", &flash_prefill_paged,
+        "MFMA flash-attention prefill of one chunk over the paged KV cache",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_table"), py::arg("ctx_len"), py::arg("scale"));
   m.def("flash_fwd_train", &flash_fwd_train,
         "MFMA flash-attention forward + log-sum-exp (training)");
   m.def("fa_bwd", &fa_bwd,

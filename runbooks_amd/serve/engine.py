@@ -11,6 +11,12 @@ when capacity allows, then all running sequences decode as one batch —
 decode batches hit the gfx950 paged-decode kernel
 (ops/csrc/attention_decode.hip).
 
+Two opt-in knobs prefill FROM the paged cache instead
+(ops/csrc/attention_prefill_paged.hip): ``prefill_from_cache`` runs only
+the uncached tail of a prompt on a prefix-cache hit, and
+``prefill_chunk`` feeds a long prompt through the model at most that
+many tokens per step, so running sequences keep decoding in between.
+
 Sliding-window attention (mistral, cfg.sliding_window): enforced here as
 pure KV bookkeeping — RoPE is applied at absolute positions when keys
 are written, so attention over any suffix of the cache is exact, and the
@@ -86,6 +92,9 @@ class Request:
     # tokens whose KV blocks were freed by the sliding window (always a
     # multiple of BLOCK_SIZE; blocks[] maps retained positions only)
     dropped: int = 0
+    # prompt tokens whose KV is in the cache (prefix hit + chunks done so
+    # far) while the request is prefilling
+    computed: int = 0
     finished: bool = False
     created: float = field(default_factory=time.time)
 
@@ -99,7 +108,9 @@ class Engine:
                  dtype=torch.bfloat16, kv_blocks: int | None = None,
                  max_batch: int = 64, mem_fraction: float = 0.85, seed: int = 0,
                  load_in_8bit: bool = False, prefix_cache: bool | None = None,
-                 kv_fp8: bool | None = None, load_in_4bit: bool = False):
+                 kv_fp8: bool | None = None, load_in_4bit: bool = False,
+                 prefill_from_cache: bool | None = None,
+                 prefill_chunk: int | None = None):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
@@ -167,6 +178,9 @@ class Engine:
         self.dummy_block = kv_blocks - 1
         self.waiting: list[Request] = []
         self.running: list[Request] = []
+        # the one request whose prompt is part-way through a chunked
+        # prefill: holds its blocks, is in neither waiting nor running
+        self.prefilling: Request | None = None
         self._next_id = 0
         # sliding window bounds per-seq blocks at W//bs + 2 (retained
         # suffix <= W + bs tokens incl. the one being appended); prompts
@@ -187,12 +201,13 @@ class Engine:
         # collective.
         self.tp = comm.world_size()
         self.use_graphs = torch.cuda.is_available() and self.tp == 1
-        # Prefix caching (opt-in, RB_PREFIX_CACHE=1 or prefix_cache=True):
-        # full 16-token prompt-prefix chunks are shared across requests by
-        # refcount — a hit skips the KV writes for those chunks (the
-        # prefill still computes the full prompt, so attention inputs are
-        # identical; the kernels are untouched, only the block table
-        # changes). Bounds cache memory for common-system-prompt serving.
+        # Prefix caching (RB_PREFIX_CACHE=0 or prefix_cache=False turns it
+        # off): full 16-token prompt-prefix chunks are shared across
+        # requests by refcount, which bounds cache memory for
+        # common-system-prompt serving. By default a hit only skips the KV
+        # writes for those chunks and the prefill still computes the full
+        # prompt; with prefill_from_cache the hit chunks are not computed
+        # at all — the rest of the prompt attends over them in the cache.
         import os as _os
         # default-on since the GPU validation pass (r2: shared-prompt
         # decode parity vs an uncached engine); RB_PREFIX_CACHE=0 disables
@@ -201,9 +216,34 @@ class Engine:
             else _os.environ.get("RB_PREFIX_CACHE", "1") == "1")
         from collections import OrderedDict
         self._pc: "OrderedDict[tuple, int]" = OrderedDict()
+        # Prefill from the paged cache (both off by default):
+        # RB_PREFILL_FROM_CACHE=1 / prefill_from_cache=True skips the
+        # cached prefix of a prompt; RB_PREFILL_CHUNK=N / prefill_chunk=N
+        # (a multiple of the block size, 0 = off) bounds the prompt tokens
+        # run per step.
+        self.prefill_from_cache = (
+            prefill_from_cache if prefill_from_cache is not None
+            else _os.environ.get("RB_PREFILL_FROM_CACHE", "0") == "1")
+        self.prefill_chunk = int(
+            prefill_chunk if prefill_chunk is not None
+            else _os.environ.get("RB_PREFILL_CHUNK", "0") or 0)
+        if self.prefill_chunk < 0 or self.prefill_chunk % self.bs:
+            raise ValueError(
+                f"prefill_chunk must be a multiple of {self.bs}, got "
+                f"{self.prefill_chunk}")
+        if (self.prefill_from_cache or self.prefill_chunk) and \
+                (self.tp > 1 or self.kv_fp8):
+            print("engine: prefill_from_cache / prefill_chunk ignored "
+                  + ("at TP>1" if self.tp > 1 else "with an fp8 KV cache")
+                  + " (paged prefill is single-GPU bf16; whole-prompt "
+                  "prefill is used)", flush=True)
+            self.prefill_from_cache = False
+            self.prefill_chunk = 0
         self.stats = {"steps": 0, "prefills": 0, "decode_tokens": 0,
                       "preemptions": 0, "prefix_hits": 0,
-                      "prefix_hit_blocks": 0, "window_dropped_blocks": 0}
+                      "prefix_hit_blocks": 0, "window_dropped_blocks": 0,
+                      "prefill_tokens": 0, "prefix_skipped_tokens": 0,
+                      "prefill_chunks": 0}
 
     def _auto_kv_blocks(self, mem_fraction: float) -> int:
         elem = (self.cfg.head_dim + 16) if self.kv_fp8 \
@@ -272,6 +312,8 @@ class Engine:
     def _admit(self) -> Request | None:
         if not self.waiting or len(self.running) >= self.max_batch:
             return None
+        if self.prefilling is not None:   # one chunked prefill at a time
+            return None
         req = self.waiting[0]
         S = len(req.prompt_ids)
         hits: list[tuple[tuple, int]] = []
@@ -307,6 +349,11 @@ class Engine:
                 return
             b = self._pc[key]
             if b in protect:
+                continue
+            if self.prefill_from_cache and self.allocator.refs[b] > 1:
+                # still shared by a live request: dropping the entry frees
+                # nothing now, and would cost that request's re-prefill
+                # its cached history if it is preempted next
                 continue
             del self._pc[key]
             before = len(self.allocator.free)
@@ -348,6 +395,11 @@ class Engine:
             from .tp_worker import broadcast_prefill
             broadcast_prefill(tokens, positions, slots)
         logits = self.model.prefill(tokens, positions, self.caches, slots)
+        return self._sample_first(req, logits)
+
+    def _sample_first(self, req: Request, logits) -> int:
+        """Sample the first output token from last-position prefill logits."""
+        S = len(req.prompt_ids)
         # a per-request seed makes sampling reproducible across runs and
         # independent of the request_id the scheduler happened to assign
         base = (req.seed * 2654435761 if req.seed is not None
@@ -359,6 +411,61 @@ class Engine:
         if req.logprobs is not None:
             self._record_logprobs(req, logits0, t)
         return t
+
+    def _prefill_paged(self, req: Request) -> int | None:
+        """Run prompt tokens [computed, end) through the model against the
+        paged cache: positions below ``computed`` (prefix-cache hit, earlier
+        chunks) are read through the request's block table, not recomputed.
+        Returns the first output token after the last chunk, else None."""
+        S = len(req.prompt_ids)
+        start = req.computed
+        end = min(S, start + self.prefill_chunk) if self.prefill_chunk else S
+        tokens = torch.tensor([req.prompt_ids[start:end]], dtype=torch.long,
+                              device=self.device)
+        positions = torch.arange(start, end, dtype=torch.int32,
+                                 device=self.device)
+        # as in _prefill: writes into shared prefix blocks go to the dummy
+        # block (only the S-1 token of a fully cached prompt lands there)
+        shared_tokens = getattr(req, "_shared_chunks", 0) * self.bs
+        slots = torch.tensor(
+            [(self.dummy_block * self.bs + i % self.bs) if i < shared_tokens
+             else req.blocks[i // self.bs] * self.bs + i % self.bs
+             for i in range(start, end)],
+            dtype=torch.int32, device=self.device)
+        nb = (end + self.bs - 1) // self.bs
+        bt = torch.tensor(req.blocks[:nb], dtype=torch.int32,
+                          device=self.device)
+        logits = self.model.prefill_paged(tokens, positions, self.caches,
+                                          slots, bt, start)
+        self.stats["prefill_tokens"] += end - start
+        if getattr(req, "_chunked", False):
+            self.stats["prefill_chunks"] += 1
+        req.computed = end
+        if end < S:
+            return None
+        return self._sample_first(req, logits)
+
+    def _prefill_step(self, req: Request) -> int | None:
+        """One step of a request's prefill: the whole prompt in one pass
+        by default; with the paged-prefill knobs, the uncached part, at
+        most prefill_chunk tokens at a time (None = more chunks to go)."""
+        if req is not self.prefilling:   # fresh from _admit
+            S = len(req.prompt_ids)
+            ctx = 0
+            if self.prefill_from_cache:
+                # at least one token is computed: its logits pick the
+                # first output token
+                ctx = min(getattr(req, "_shared_chunks", 0) * self.bs, S - 1)
+            req._chunked = bool(self.prefill_chunk
+                                and S - ctx > self.prefill_chunk)
+            if ctx == 0 and not req._chunked:
+                tok = self._prefill(req)
+                self.stats["prefill_tokens"] += S
+                req.computed = S
+                return tok
+            req.computed = ctx
+            self.stats["prefix_skipped_tokens"] += ctx
+        return self._prefill_paged(req)
 
     def _decode_batch(self, reqs: list[Request]) -> list[int]:
         B = len(reqs)
@@ -473,13 +580,21 @@ class Engine:
         return False
 
     def cancel(self, request_id: int) -> bool:
-        """Stop a request: waiting -> dropped now; running -> finishes at
-        the next scheduler sweep."""
+        """Stop a request: waiting -> dropped now; part-way through a
+        chunked prefill -> dropped now, blocks released; running ->
+        finishes at the next scheduler sweep."""
         for r in self.waiting:
             if r.request_id == request_id:
                 self.waiting.remove(r)
                 r.finished = True
                 return True
+        r = self.prefilling
+        if r is not None and r.request_id == request_id:
+            self.prefilling = None
+            self.allocator.release(r.blocks)
+            r.blocks = []
+            r.finished = True
+            return True
         for r in self.running:
             if r.request_id == request_id:
                 r.max_new_tokens = max(1, len(r.output_ids))
@@ -494,7 +609,10 @@ class Engine:
         # sweep first: requests already satisfied (cancel() capped their
         # max_new_tokens between steps) must not decode one extra token
         self._sweep_finished(finished)
-        req = self._admit()
+        # a prefill in flight takes its next chunk before anything new is
+        # admitted
+        req = self.prefilling if self.prefilling is not None \
+            else self._admit()
         if req is None and not self.running and self.waiting:
             head = self.waiting[0]
             need = (len(head.prompt_ids) + self.bs - 1) // self.bs + 1
@@ -517,18 +635,25 @@ class Engine:
                 if tr:
                     with tr.span("prefill", tokens=len(req.prompt_ids),
                                  request=req.request_id):
-                        first = self._prefill(req)
+                        first = self._prefill_step(req)
                 else:
-                    first = self._prefill(req)
+                    first = self._prefill_step(req)
             except Exception:
                 # _admit already popped req from waiting and allocated its
                 # blocks; releasing here (shared prefix blocks are
                 # refcounted, release decrements) keeps a failing request
                 # from leaking KV pool forever.
+                self.prefilling = None
                 self.allocator.release(req.blocks)
                 req.blocks = []
                 req.finished = True
                 raise
+            if first is None:
+                # more chunks to go: keep the blocks, decode the running
+                # sequences, continue next step
+                self.prefilling = req
+                break
+            self.prefilling = None
             self.stats["prefills"] += 1
             if self.prefix_cache_enabled:
                 self._pc_insert(req)
@@ -586,7 +711,8 @@ class Engine:
                 finished.append(r)
 
     def has_work(self) -> bool:
-        return bool(self.waiting or self.running)
+        return bool(self.waiting or self.running
+                    or self.prefilling is not None)
 
     # -- convenience --------------------------------------------------------------
     def generate(self, prompt_ids: list[int], max_new_tokens: int = 64,

@@ -146,17 +146,23 @@ class EngineLoop:
                     # that keeps crashing the step) fail everything rather
                     # than spin
                     self._failures += 1
+                    # a request part-way through a chunked prefill is in
+                    # neither queue
+                    pre = ([self.engine.prefilling]
+                           if self.engine.prefilling is not None else [])
                     if self._failures >= 3:
                         for r in (self.engine.running +
-                                  self.engine.waiting):
+                                  self.engine.waiting + pre):
                             r.finished = True
                             if r.blocks:
                                 self.engine.allocator.release(r.blocks)
                                 r.blocks = []
                         self.engine.running.clear()
                         self.engine.waiting.clear()
+                        self.engine.prefilling = None
+                        pre = []
                     alive = {r.request_id for r in
-                             self.engine.running + self.engine.waiting}
+                             self.engine.running + self.engine.waiting + pre}
                     for rid in list(self._watchers):
                         if rid not in alive:
                             self._watchers.pop(rid).put(None)

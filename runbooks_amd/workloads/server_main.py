@@ -90,8 +90,20 @@ def main():
                             os.environ.get("KV_FP8", "")).lower() in \
         ("1", "true")
     in_4bit = os.environ.get("MODEL_LOAD_IN_4BIT", "").lower() in ("1", "true")
+    # PARAM_PREFILL_FROM_CACHE / PREFILL_FROM_CACHE: a prefix-cache hit
+    # skips the cached part of the prompt instead of recomputing it
+    from_cache = os.environ.get(
+        "PARAM_PREFILL_FROM_CACHE",
+        os.environ.get("PREFILL_FROM_CACHE", "")).lower() in ("1", "true")
+    # PARAM_PREFILL_CHUNK / PREFILL_CHUNK: prompt tokens run per engine
+    # step (a multiple of 16; 0 or unset = whole prompt in one pass)
+    chunk = int(os.environ.get("PARAM_PREFILL_CHUNK",
+                               os.environ.get("PREFILL_CHUNK", "")) or 0)
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
-                    kv_fp8=kv_fp8)
+                    kv_fp8=kv_fp8,
+                    # unset leaves the engine's own RB_* env defaults
+                    prefill_from_cache=from_cache or None,
+                    prefill_chunk=chunk or None)
     tok = load_tokenizer(model_dir if model_dir.exists() else None)
     if comm.rank() == 0:
         serve_forever(engine, tok, port=int(os.environ.get("PORT", "8080")),
