@@ -19,23 +19,18 @@
 //        dK += dS^T Q                  mfma(A=QT_lds, B=repack(dS))
 //                                                               C[d][key]
 //
-// Same wave geometry as the forward (attention_prefill.hip): 8 waves per
-// WG, each wave owns 32 rows of its output on lanes (j = lane&31), the
-// MFMA C reg dim carries the other axis. The C->B "repack" (pack_bf16 +
-// v_permlane32_swap) is the forward's P repack. GQA: dK/dV are computed
-// per q-head ([B,S,Hq,DH]); the group-sum to Hkv heads happens in the
-// Python wrapper (ops/attention.py) — llama2-7b is MHA so the common path
-// has no extra reduction.
-//
-// mfma_f32_32x32x16_bf16 layouts (cdna_hip_programming.md §3):
-//   A[i][k]: i = lane&31, k = (lane>>5)*8 + e
-//   B[k][j]: j = lane&31, k = (lane>>5)*8 + e
-//   C[i][j]: j = lane&31, i = (r&3) + 8*(r>>2) + 4*(lane>>5)
+// Wave geometry as in the forward (flash_fwd_core.h), with 4 waves per WG:
+// each wave owns 32 rows of its output on lanes (j = lane&31), the MFMA C
+// reg dim carries the other axis. The fragment maps and the C->B "repack"
+// the forward uses for P are shared with it (mfma_frag.h). GQA: dK/dV are
+// computed per q-head ([B,S,Hq,DH]); the group-sum to Hkv heads happens in
+// the Python wrapper (ops/attention.py) — llama2-7b is MHA so the common
+// path has no extra reduction.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
-#include "common.h"
+#include "mfma_frag.h"
 
 namespace {
 
@@ -44,35 +39,9 @@ constexpr int BLOCK = 256;  // 4 waves (128-row WGs: finer grid
                             // doubles WG count vs 8-wave WGs)
 constexpr int TILE = 64;    // rows staged to LDS per loop step
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
-typedef __attribute__((ext_vector_type(16))) float f32x16v;
-
-RB_DEV unsigned pack2_bf16(float lo, float hi) {
-  union { __bf16 b; unsigned short u; } a, b;
-  a.b = (__bf16)lo;
-  b.b = (__bf16)hi;
-  return ((unsigned)b.u << 16) | a.u;
-}
-
-RB_DEV bf16x8v words_to_frag(unsigned w0, unsigned w1, unsigned w2,
-                             unsigned w3) {
-  union { unsigned u[4]; bf16x8v v; } c;
-  c.u[0] = w0; c.u[1] = w1; c.u[2] = w2; c.u[3] = w3;
-  return c.v;
-}
-
-// C-layout values (16 regs = 32 i-rows) -> two B fragments along k.
-// Identical to the forward's P repack; kslot selects k in [0,16)/[16,32).
-RB_DEV bf16x8v repack_c_to_b(const float *p, int kslot) {
-  const int r0 = kslot * 8;
-  unsigned pk0 = pack2_bf16(p[r0 + 0], p[r0 + 1]);
-  unsigned pk1 = pack2_bf16(p[r0 + 2], p[r0 + 3]);
-  unsigned pk2 = pack2_bf16(p[r0 + 4], p[r0 + 5]);
-  unsigned pk3 = pack2_bf16(p[r0 + 6], p[r0 + 7]);
-  auto r02 = __builtin_amdgcn_permlane32_swap(pk0, pk2, false, false);
-  auto r13 = __builtin_amdgcn_permlane32_swap(pk1, pk3, false, false);
-  return words_to_frag(r02[0], r13[0], r02[1], r13[1]);
-}
+using rb::bf16x8v;
+using rb::f32x16v;
+using rb::repack_c_to_b;
 
 // ---------------------------------------------------------------------------
 // 1. D = rowsum(dO . O): dO, O [B, S, H, DH] bf16 -> D [B, H, S] f32

@@ -23,6 +23,8 @@ NAN = float("nan")
     (272, 300, 4, 1, 64, False),   # MQA, two workgroups, many tiles
     (16, 1, 2, 2, 256, False),     # single query row, wide heads
     (100, 33, 8, 2, 64, True),     # ctx off the block grid, 2 waves
+    (80, 40, 2, 1, 256, True),     # wide heads, transposed V, ctx off the tiles
+    (40, 270, 2, 2, 128, False),   # prefix, two workgroups, the second ragged
 ])
 def test_paged_prefill_kernel(ctx, T, Hq, Hkv, dh, vt):
     assert ops.has_hip()
