@@ -3,8 +3,9 @@
 random weights, one GPU).
 
     python benchmarks/prefix_ttft.py [--rounds 2] [--out FILE.json]
+                                     [--experiments prefix,chunk,burst]
 
-Two experiments, each run in alternating fresh child processes so neither
+Three experiments, each run in alternating fresh child processes so neither
 setting inherits a warm allocator, graph or library state from the other:
 
 * prefix: requests share a 1024-token prefix and add 64 tokens of their
@@ -15,6 +16,12 @@ setting inherits a warm allocator, graph or library state from the other:
   largest single step() time until its first token is reported for
   prefill_chunk 0 and 512, next to the plain decode step time. An untimed
   4096-token prompt runs first so library warm-up is not in the figure.
+* burst: eight requests arrive together and the time until all eight have
+  their first token is reported, with prefill_batch 0 (eight forwards in
+  one step, max_prefills_per_step=8) and 8 (one packed forward). "shared":
+  after one request has filled a 1024-token prefix, each of the eight adds
+  64 own tokens (prefill_from_cache on in both settings). "cold": eight
+  unrelated 256-token prompts. An untimed burst of each kind runs first.
 
 Times are host clocks around step(), which ends in a device sync.
 Prints one JSON line.
@@ -98,11 +105,64 @@ def child_chunk(chunk: int) -> dict:
             "total_ms": round(sum(worst), 2)}
 
 
+BURST, COLD, REPEATS = 8, 256, 3
+
+
+def child_burst(batch: int) -> dict:
+    import torch
+
+    from runbooks_amd.serve import Engine
+    eng = Engine(MODEL, kv_blocks=3072, seed=1, prefix_cache=True,
+                 prefill_from_cache=True, prefill_chunk=0,
+                 prefill_batch=batch)
+    eng.max_prefills_per_step = BURST
+    g = torch.Generator().manual_seed(0)
+    vocab = eng.cfg.vocab_size
+
+    def rand(n):
+        return torch.randint(1, vocab, (n,), generator=g).tolist()
+
+    def burst(prompts):
+        reqs = [eng.submit(p, max_new_tokens=1) for p in prompts]
+        ms, steps = 0.0, 0
+        while not all(r.finished for r in reqs):
+            ms += _timed_step(eng, torch)
+            steps += 1
+        assert all(len(r.output_ids) == 1 for r in reqs)
+        return ms, steps
+
+    shared_ms, cold_ms, steps = [], [], set()
+    for i in range(REPEATS + 1):            # the first of each only warms up
+        shared = rand(PREFIX)
+        fill = eng.submit(shared + rand(UNIQUE), max_new_tokens=1)
+        while not fill.finished:
+            eng.step()
+        skipped0 = eng.stats["prefix_skipped_tokens"]
+        ms_s, n_s = burst([shared + rand(UNIQUE) for _ in range(BURST)])
+        assert eng.stats["prefix_skipped_tokens"] - skipped0 == BURST * PREFIX
+        ms_c, n_c = burst([rand(COLD) for _ in range(BURST)])
+        eng.flush_prefix_cache()
+        if i:
+            shared_ms.append(ms_s)
+            cold_ms.append(ms_c)
+            steps.update((n_s, n_c))
+    assert steps == {1}, steps              # every burst is one step()
+    assert eng.stats["prefill_batches"] == (2 * (REPEATS + 1) if batch > 1
+                                            else 0)
+    return {"prefill_batch": batch,
+            "shared_ms": [round(x, 2) for x in shared_ms],
+            "shared_ms_median": round(statistics.median(shared_ms), 2),
+            "cold_ms": [round(x, 2) for x in cold_ms],
+            "cold_ms_median": round(statistics.median(cold_ms), 2)}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--rounds", type=int, default=2)
     p.add_argument("--out", default=None)
-    p.add_argument("--child", choices=["prefix", "chunk"], default=None)
+    p.add_argument("--experiments", default="prefix,chunk,burst")
+    p.add_argument("--child", choices=["prefix", "chunk", "burst"],
+                   default=None)
     p.add_argument("--value", type=int, default=0)
     args = p.parse_args()
     if args.child == "prefix":
@@ -110,6 +170,10 @@ def main():
         return
     if args.child == "chunk":
         print("RESULT " + json.dumps(child_chunk(args.value)))
+        return
+
+    if args.child == "burst":
+        print("RESULT " + json.dumps(child_burst(args.value)))
         return
 
     def run(kind, value):
@@ -121,16 +185,20 @@ def main():
             raise SystemExit(f"{kind} child (value {value}) failed: "
                              f"exit {r.returncode}")
         line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+        print(f"{kind} {value}: done", file=sys.stderr, flush=True)
         return json.loads(line[-1][len("RESULT "):])
 
     res = {"model": MODEL, "prefix_tokens": PREFIX, "unique_tokens": UNIQUE,
-           "long_prompt": LONG, "prefix": [], "chunk": []}
-    for _ in range(args.rounds):
-        for v in (0, 1):
-            res["prefix"].append(run("prefix", v))
-    for _ in range(args.rounds):
-        for v in (0, CHUNK):
-            res["chunk"].append(run("chunk", v))
+           "long_prompt": LONG, "burst_requests": BURST,
+           "cold_tokens": COLD, "prefix": [], "chunk": [], "burst": []}
+    todo = args.experiments.split(",")
+    for kind, values in (("prefix", (0, 1)), ("chunk", (0, CHUNK)),
+                         ("burst", (0, BURST))):
+        if kind not in todo:
+            continue
+        for _ in range(args.rounds):
+            for v in values:
+                res[kind].append(run(kind, v))
     line = json.dumps(res)
     print(line)
     if args.out:

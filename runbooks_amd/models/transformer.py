@@ -14,6 +14,8 @@ Forward modes:
                                       last-position logits
   * ``prefill_paged(...)``          — one chunk of one prompt whose earlier
                                       positions are already in the cache
+  * ``prefill_paged_batch(...)``    — the same for several prompts' chunks
+                                      packed into one token dimension
   * ``decode(...)``                 — one token per sequence against the
                                       paged cache (gfx950 decode kernel)
 
@@ -126,6 +128,18 @@ class Attention(nn.Module):
         ops.kv_append(k, v, kc, vc, slot_mapping)
         o = ops.paged_prefill(q, kc, vc, block_table, ctx_len,
                               scale=self.scale)
+        return self.o_proj(o.reshape(T, self.hq * self.dh))
+
+    def forward_prefill_paged_batch(self, x, cos, sin, positions, kc, vc,
+                                    slot_mapping, block_tables, plan):
+        """Several sequences' chunks packed in x [Ttot, hidden]: append all
+        their k/v (per token), then attend each sequence through its own
+        block-table row and context length (ops.paged_prefill_plan)."""
+        T = x.shape[0]
+        q, k, v = self._qkv(x, cos, sin, positions)
+        ops.kv_append(k, v, kc, vc, slot_mapping)
+        o = ops.paged_prefill_batch(q, kc, vc, block_tables, plan,
+                                    scale=self.scale)
         return self.o_proj(o.reshape(T, self.hq * self.dh))
 
     def forward_decode(self, x, cos, sin, positions, kc, vc, slot_mapping,
@@ -429,6 +443,29 @@ class Transformer(nn.Module):
                 slot_mapping, block_table, ctx_len)
             x = blk(x, fn)
         x = self.norm_f(x.view(1, T, -1)[:, -1])
+        logits = self.lm_head(x)
+        return gather_from_tp(logits) if self._lm_vocab_parallel else logits
+
+    @torch.no_grad()
+    def prefill_paged_batch(self, tokens, positions, caches, slot_mapping,
+                            block_tables, plan):
+        """Prefill the chunks of B sequences in one pass. tokens [Ttot],
+        absolute positions [Ttot] and slot_mapping [Ttot] are the chunks
+        packed back to back as ``plan`` (ops.paged_prefill_plan) lays them
+        out; sequence b's first ``plan.ctx_lens[b]`` positions are already
+        in the paged cache and ``block_tables`` (int32 [B, maxb]) row b
+        maps the whole of it. Returns each sequence's last-position logits
+        [B, V]."""
+        assert tokens.dim() == 1 and tokens.shape[0] == plan.total, \
+            "prefill_paged_batch takes the plan's packed tokens"
+        x = self._embed(tokens, positions)
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_prefill_paged_batch(  # noqa: E731
+                h, self.rope_cos, self.rope_sin, positions, kc, vc,
+                slot_mapping, block_tables, plan)
+            x = blk(x, fn)
+        # only each sequence's last row reaches the vocabulary GEMM
+        x = self.norm_f(x.index_select(0, plan.last_rows()))
         logits = self.lm_head(x)
         return gather_from_tp(logits) if self._lm_vocab_parallel else logits
 

@@ -14,6 +14,10 @@
 * ``paged_prefill``: one chunk of one sequence's prompt attending over the
   paged KV cache (cached prefix + the chunk itself) — gfx950 MFMA kernel
   on GPU (csrc/attention_prefill_paged.hip), fp32 reference on CPU.
+
+* ``paged_prefill_batch``: the same for several sequences' chunks packed
+  into one token dimension, one launch; lengths come from a host-built
+  ``paged_prefill_plan``.
 """
 from __future__ import annotations
 
@@ -208,6 +212,133 @@ def paged_prefill(q, k_cache, v_cache, block_table, ctx_len,
             block_table.to(torch.int32).contiguous(), int(ctx_len),
             float(scale))
     return paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale)
+
+
+class PagedPrefillPlan:
+    """Host-side description of one packed ("varlen") paged prefill:
+    sequence b owns packed rows [cu_q[b], cu_q[b+1]) and has ctx_lens[b]
+    keys cached before them. ``cpu`` is the int32 tensor
+    [cu_q (B+1) | ctx_lens (B) | tile_seq (ntiles) | tile_row0 (ntiles)]
+    — one 256-row kernel tile per entry, never spanning two sequences —
+    and ``dev`` its copy on the device (None for a CPU plan). Build it with
+    ``paged_prefill_plan``; it is immutable and shared by every layer of a
+    forward."""
+
+    __slots__ = ("q_lens", "ctx_lens", "cu_q", "num_seqs", "total",
+                 "ntiles", "cpu", "dev")
+
+    def __init__(self, q_lens, ctx_lens, device):
+        q_lens = [int(t) for t in q_lens]
+        ctx_lens = [int(c) for c in ctx_lens]
+        if not q_lens or len(q_lens) != len(ctx_lens):
+            raise ValueError("paged_prefill_plan: q_lens and ctx_lens must "
+                             "be equally long and not empty")
+        for t, c in zip(q_lens, ctx_lens):
+            if t < 1 or c < 0 or c + t >= 1 << 30:
+                raise ValueError(
+                    f"paged_prefill_plan: need T >= 1, ctx >= 0 and "
+                    f"ctx + T < 2^30, got T={t}, ctx={c}")
+        cu = [0]
+        for t in q_lens:
+            cu.append(cu[-1] + t)
+        if cu[-1] >= 1 << 30:
+            raise ValueError("paged_prefill_plan: too many packed rows")
+        tile_seq, tile_row0 = [], []
+        for b, t in enumerate(q_lens):
+            for r0 in range(0, t, 256):
+                tile_seq.append(b)
+                tile_row0.append(r0)
+        self.q_lens = tuple(q_lens)
+        self.ctx_lens = tuple(ctx_lens)
+        self.cu_q = tuple(cu)
+        self.num_seqs = len(q_lens)
+        self.total = cu[-1]
+        self.ntiles = len(tile_seq)
+        self.cpu = torch.tensor(cu + ctx_lens + tile_seq + tile_row0,
+                                dtype=torch.int32)
+        dev = torch.device(device)
+        # the forward's one host-to-device copy of the lengths
+        self.dev = self.cpu.to(dev) if dev.type != "cpu" else None
+
+    def last_rows(self) -> torch.Tensor:
+        """Packed index of each sequence's last row, int64 [B], on the
+        plan's device (derived from the copy already there)."""
+        t = self.dev if self.dev is not None else self.cpu
+        return t[1:self.num_seqs + 1].long() - 1
+
+    def max_blocks(self, block_size: int = 16) -> int:
+        """Block-table width the longest sequence needs."""
+        return max((c + t + block_size - 1) // block_size
+                   for t, c in zip(self.q_lens, self.ctx_lens))
+
+
+def paged_prefill_plan(q_lens, ctx_lens, device) -> PagedPrefillPlan:
+    """Plan a packed paged prefill from host ints: q_lens[b] rows of
+    sequence b follow its ctx_lens[b] cached keys. Built once per model
+    forward (one small host-to-device copy) and passed to every layer's
+    ``paged_prefill_batch``."""
+    return PagedPrefillPlan(q_lens, ctx_lens, device)
+
+
+def _check_batch_shapes(q, block_tables, plan):
+    if q.dim() != 3 or q.shape[0] != plan.total:
+        raise ValueError(
+            f"paged_prefill_batch: q has {tuple(q.shape)} rows/shape, the "
+            f"plan packs {plan.total} rows")
+    if block_tables.dim() != 2 or block_tables.shape[0] != plan.num_seqs:
+        raise ValueError(
+            f"paged_prefill_batch: block_tables {tuple(block_tables.shape)} "
+            f"for a plan of {plan.num_seqs} sequences")
+    if block_tables.shape[1] < plan.max_blocks():
+        raise ValueError(
+            f"paged_prefill_batch: block_tables has {block_tables.shape[1]} "
+            f"columns, the longest sequence needs {plan.max_blocks()}")
+
+
+def paged_prefill_batch_ref(q, k_cache, v_cache, block_tables, plan,
+                            scale=None):
+    """fp32 reference for paged_prefill_batch: paged_prefill_ref on each
+    sequence's rows, table row and context length."""
+    _check_batch_shapes(q, block_tables, plan)
+    out = torch.empty_like(q)
+    for b in range(plan.num_seqs):
+        lo, hi = plan.cu_q[b], plan.cu_q[b + 1]
+        out[lo:hi] = paged_prefill_ref(q[lo:hi], k_cache, v_cache,
+                                       block_tables[b], plan.ctx_lens[b],
+                                       scale)
+    return out
+
+
+def paged_prefill_batch(q, k_cache, v_cache, block_tables, plan,
+                        scale: float | None = None):
+    """Causal attention of several sequences' prompt chunks, packed back to
+    back in q [Ttot, Hq, Dh], over the paged cache in one launch.
+
+    ``plan`` (paged_prefill_plan) holds each sequence's row count and
+    cached context; ``block_tables`` int32 [B, >= longest sequence's
+    blocks], row b valid below ceil((ctx_b + T_b)/16) — entries past that
+    are never read. Every chunk's own k/v must already be appended. GPU:
+    the gfx950 MFMA kernel, each sequence bit-identical to ``paged_prefill``
+    on it alone; all lengths are checked on the host, nothing waits for the
+    device. fp8 caches raise. CPU: fp32 reference.
+    """
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _backend.use_hip(q):
+        if k_cache.dtype == torch.uint8:
+            raise NotImplementedError(
+                "paged_prefill_batch: fp8 KV caches are not supported")
+        if plan.dev is None or plan.dev.device != q.device:
+            raise ValueError("paged_prefill_batch: the plan was built for "
+                             "another device than q's")
+        _check_batch_shapes(q, block_tables, plan)
+        if block_tables.dtype != torch.int32:
+            block_tables = block_tables.to(torch.int32)
+        return _backend.ext().flash_prefill_paged_batch(
+            q.contiguous(), k_cache, v_cache, block_tables.contiguous(),
+            plan.dev, plan.cpu, plan.num_seqs, float(scale))
+    return paged_prefill_batch_ref(q, k_cache, v_cache, block_tables, plan,
+                                   scale)
 
 
 def _is_vt(k_cache, v_cache) -> bool:

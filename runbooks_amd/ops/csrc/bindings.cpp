@@ -50,6 +50,10 @@ std::vector<at::Tensor> paged_decode_swz(at::Tensor q, at::Tensor k_cache,
 at::Tensor flash_prefill(at::Tensor q, at::Tensor k, at::Tensor v, double scale);
 at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                                at::Tensor block_table, int64_t ctx_len, double scale);
+at::Tensor flash_prefill_paged_batch(at::Tensor q, at::Tensor k_cache,
+                                     at::Tensor v_cache, at::Tensor block_tables,
+                                     at::Tensor plan_dev, at::Tensor plan_cpu,
+                                     int64_t B, double scale);
 std::vector<at::Tensor> flash_fwd_train(at::Tensor q, at::Tensor k, at::Tensor v,
                                         double scale);
 std::vector<at::Tensor> fa_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
@@ -144,6 +148,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MFMA flash-attention prefill of one chunk over the paged KV cache",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_table"), py::arg("ctx_len"), py::arg("scale"));
+  m.def("flash_prefill_paged_batch", &flash_prefill_paged_batch,
+        "MFMA flash-attention prefill of several sequences' packed chunks "
+        "over the paged KV cache",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("plan_dev"), py::arg("plan_cpu"),
+        py::arg("num_seqs"), py::arg("scale"));
   m.def("flash_fwd_train", &flash_fwd_train,
         "MFMA flash-attention forward + log-sum-exp (training)");
   m.def("fa_bwd", &fa_bwd,

@@ -16,6 +16,14 @@ Two opt-in knobs prefill FROM the paged cache instead
 the uncached tail of a prompt on a prefix-cache hit, and
 ``prefill_chunk`` feeds a long prompt through the model at most that
 many tokens per step, so running sequences keep decoding in between.
+A third, ``prefill_batch`` = N > 1, admits up to N waiting requests per
+step and runs their (uncached) prompt tokens packed into ONE model
+forward (``Transformer.prefill_paged_batch``, the varlen kernel in the
+same file) instead of one forward each: a burst of short tails behind a
+shared system prompt streams the weights once. A request that would hit
+on a prefix another member of the same batch is about to publish waits
+one step and hits; a prompt longer than ``prefill_chunk`` still takes the
+chunked path alone.
 
 Sliding-window attention (mistral, cfg.sliding_window): enforced here as
 pure KV bookkeeping — RoPE is applied at absolute positions when keys
@@ -110,7 +118,8 @@ class Engine:
                  load_in_8bit: bool = False, prefix_cache: bool | None = None,
                  kv_fp8: bool | None = None, load_in_4bit: bool = False,
                  prefill_from_cache: bool | None = None,
-                 prefill_chunk: int | None = None):
+                 prefill_chunk: int | None = None,
+                 prefill_batch: int | None = None):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
@@ -239,11 +248,28 @@ class Engine:
                   "prefill is used)", flush=True)
             self.prefill_from_cache = False
             self.prefill_chunk = 0
+        # Batched prefill (off by default): RB_PREFILL_BATCH=N /
+        # prefill_batch=N > 1 packs up to N admissions of a step into one
+        # model forward; prefill_chunk, when set, is also that forward's
+        # token budget. 0 or 1 = one forward per request.
+        self.prefill_batch = int(
+            prefill_batch if prefill_batch is not None
+            else _os.environ.get("RB_PREFILL_BATCH", "0") or 0)
+        if self.prefill_batch < 0:
+            raise ValueError(
+                f"prefill_batch must be >= 0, got {self.prefill_batch}")
+        if self.prefill_batch > 1 and (self.tp > 1 or self.kv_fp8):
+            print("engine: prefill_batch ignored "
+                  + ("at TP>1" if self.tp > 1 else "with an fp8 KV cache")
+                  + " (paged prefill is single-GPU bf16; one prefill per "
+                  "request is used)", flush=True)
+            self.prefill_batch = 0
         self.stats = {"steps": 0, "prefills": 0, "decode_tokens": 0,
                       "preemptions": 0, "prefix_hits": 0,
                       "prefix_hit_blocks": 0, "window_dropped_blocks": 0,
                       "prefill_tokens": 0, "prefix_skipped_tokens": 0,
-                      "prefill_chunks": 0}
+                      "prefill_chunks": 0, "prefill_batches": 0,
+                      "prefill_batched_requests": 0}
 
     def _auto_kv_blocks(self, mem_fraction: float) -> int:
         elem = (self.cfg.head_dim + 16) if self.kv_fp8 \
@@ -467,6 +493,105 @@ class Engine:
             self.stats["prefix_skipped_tokens"] += ctx
         return self._prefill_paged(req)
 
+    def _prefill_ctx(self, req: Request) -> int:
+        """Prompt tokens of a freshly admitted request that are read from
+        the cache instead of computed (at least one token is computed)."""
+        if not self.prefill_from_cache:
+            return 0
+        return min(getattr(req, "_shared_chunks", 0) * self.bs,
+                   len(req.prompt_ids) - 1)
+
+    def _admit_batch(self) -> list[Request]:
+        """prefill_batch mode: admit up to prefill_batch waiting requests,
+        FIFO, through _admit. Stops at the first that does not fit (pool,
+        max_batch, the prefill_chunk token budget) or that would hit on a
+        prefix a member of this batch is about to publish — it stays in
+        ``waiting`` and hits next step. A prompt whose own remainder
+        exceeds prefill_chunk is returned alone (chunked path) when first,
+        and ends the batch otherwise."""
+        batch: list[Request] = []
+        publish: set[tuple] = set()
+        total = 0
+        while self.waiting and len(batch) < self.prefill_batch and \
+                len(self.running) + len(batch) < self.max_batch:
+            cand = self.waiting[0]
+            S = len(cand.prompt_ids)
+            hits = 0
+            if self.prefix_cache_enabled:
+                while (hits + 1) * self.bs <= S and \
+                        tuple(cand.prompt_ids[:(hits + 1) * self.bs]) \
+                        in self._pc:
+                    hits += 1
+                if (hits + 1) * self.bs <= S and \
+                        tuple(cand.prompt_ids[:(hits + 1) * self.bs]) \
+                        in publish:
+                    break
+            rem = S - (min(hits * self.bs, S - 1)
+                       if self.prefill_from_cache else 0)
+            # prefill_chunk is the packed forward's token budget
+            alone = bool(self.prefill_chunk) and rem > self.prefill_chunk
+            if batch and (alone or (self.prefill_chunk and
+                                    total + rem > self.prefill_chunk)):
+                break
+            req = self._admit()
+            if req is None:
+                break
+            batch.append(req)
+            if alone:
+                break           # chunk by chunk, through _prefill_step
+            total += rem
+            if self.prefix_cache_enabled:
+                for k in range(hits + 1, S // self.bs + 1):
+                    publish.add(tuple(req.prompt_ids[:k * self.bs]))
+        return batch
+
+    def _prefill_batch(self, reqs: list[Request]) -> list[int]:
+        """One packed forward over the uncached prompt tokens of several
+        freshly admitted requests; returns each one's first output token."""
+        dev = self.device
+        toks: list[int] = []
+        pos: list[int] = []
+        slots: list[int] = []
+        q_lens: list[int] = []
+        ctx_lens: list[int] = []
+        for r in reqs:
+            S = len(r.prompt_ids)
+            ctx = self._prefill_ctx(r)
+            # as in _prefill: writes into shared prefix blocks go to the
+            # dummy block
+            shared_tokens = getattr(r, "_shared_chunks", 0) * self.bs
+            toks.extend(r.prompt_ids[ctx:])
+            pos.extend(range(ctx, S))
+            slots.extend(
+                (self.dummy_block * self.bs + i % self.bs)
+                if i < shared_tokens
+                else r.blocks[i // self.bs] * self.bs + i % self.bs
+                for i in range(ctx, S))
+            q_lens.append(S - ctx)
+            ctx_lens.append(ctx)
+        plan = ops.paged_prefill_plan(q_lens, ctx_lens, dev)
+        # rows are padded with the dummy block: never read, always valid
+        bt = torch.full((len(reqs), plan.max_blocks(self.bs)),
+                        self.dummy_block, dtype=torch.int32)
+        for i, r in enumerate(reqs):
+            nb = (len(r.prompt_ids) + self.bs - 1) // self.bs
+            bt[i, :nb] = torch.tensor(r.blocks[:nb], dtype=torch.int32)
+        logits = self.model.prefill_paged_batch(
+            torch.tensor(toks, dtype=torch.long, device=dev),
+            torch.tensor(pos, dtype=torch.int32, device=dev), self.caches,
+            torch.tensor(slots, dtype=torch.int32, device=dev),
+            bt.to(dev), plan)
+        first = [self._sample_first(r, logits[i:i + 1])
+                 for i, r in enumerate(reqs)]
+        for r, t, c in zip(reqs, q_lens, ctx_lens):
+            r._chunked = False
+            r.computed = len(r.prompt_ids)
+            self.stats["prefill_tokens"] += t
+            self.stats["prefix_skipped_tokens"] += c
+        self.stats["prefill_batches"] += 1
+        self.stats["prefill_batched_requests"] += len(reqs)
+        return first
+
     def _decode_batch(self, reqs: list[Request]) -> list[int]:
         B = len(reqs)
         dev = self.device
@@ -611,9 +736,42 @@ class Engine:
         self._sweep_finished(finished)
         # a prefill in flight takes its next chunk before anything new is
         # admitted
-        req = self.prefilling if self.prefilling is not None \
-            else self._admit()
-        if req is None and not self.running and self.waiting:
+        tr = get_tracer()
+        # prefill_batch mode: one prefill forward per step — the next chunk
+        # of a prefill in flight, else a packed one for two or more
+        # admissions, else the single-request path below for one
+        batched = self.prefill_batch > 1
+        batch: list[Request] = []
+        if batched and self.prefilling is None:
+            batch = self._admit_batch()
+            req = batch[0] if len(batch) == 1 else None
+        else:
+            req = self.prefilling if self.prefilling is not None \
+                else self._admit()
+        if len(batch) > 1:
+            try:
+                if tr:
+                    with tr.span(
+                            "prefill_batch", requests=len(batch),
+                            tokens=sum(len(r.prompt_ids) for r in batch)):
+                        firsts = self._prefill_batch(batch)
+                else:
+                    firsts = self._prefill_batch(batch)
+            except Exception:
+                # as for a single prefill: no member may leak its blocks
+                for r in batch:
+                    self.allocator.release(r.blocks)
+                    r.blocks = []
+                    r.finished = True
+                raise
+            for r, first in zip(batch, firsts):
+                self.stats["prefills"] += 1
+                if self.prefix_cache_enabled:
+                    self._pc_insert(r)
+                r.output_ids.append(first)
+                self.running.append(r)
+            self._sweep_finished(finished)
+        if req is None and not batch and not self.running and self.waiting:
             head = self.waiting[0]
             need = (len(head.prompt_ids) + self.bs - 1) // self.bs + 1
             if self.prefix_cache_enabled:
@@ -628,7 +786,6 @@ class Engine:
                 raise RuntimeError(
                     f"prompt of {len(r.prompt_ids)} tokens cannot fit the KV "
                     f"cache ({self.allocator.num_blocks} blocks)")
-        tr = get_tracer()
         n_admitted = 0
         while req is not None:
             try:
@@ -662,8 +819,8 @@ class Engine:
             # the prefill token may already satisfy the request
             self._sweep_finished(finished)
             n_admitted += 1
-            req = (self._admit()
-                   if n_admitted < self.max_prefills_per_step else None)
+            req = (self._admit() if not batched and
+                   n_admitted < self.max_prefills_per_step else None)
         # decode every step — admissions must not starve running
         # sequences (a freshly prefilled request decodes its second
         # token in the same step it was admitted)

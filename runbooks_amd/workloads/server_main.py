@@ -99,11 +99,16 @@ def main():
     # step (a multiple of 16; 0 or unset = whole prompt in one pass)
     chunk = int(os.environ.get("PARAM_PREFILL_CHUNK",
                                os.environ.get("PREFILL_CHUNK", "")) or 0)
+    # PARAM_PREFILL_BATCH / PREFILL_BATCH: admissions packed into one
+    # prefill forward per engine step (0, 1 or unset = one forward each)
+    pbatch = int(os.environ.get("PARAM_PREFILL_BATCH",
+                                os.environ.get("PREFILL_BATCH", "")) or 0)
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
                     kv_fp8=kv_fp8,
                     # unset leaves the engine's own RB_* env defaults
                     prefill_from_cache=from_cache or None,
-                    prefill_chunk=chunk or None)
+                    prefill_chunk=chunk or None,
+                    prefill_batch=pbatch or None)
     tok = load_tokenizer(model_dir if model_dir.exists() else None)
     if comm.rank() == 0:
         serve_forever(engine, tok, port=int(os.environ.get("PORT", "8080")),
