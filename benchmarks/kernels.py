@@ -50,9 +50,21 @@ def row(name, shape, us, bytes_moved, flops=0):
             "TF/s": round(flops / (us * 1e-6) / 1e12, 1) if flops else None}
 
 
+def report(out, args):
+    for r in out:
+        print(f"{r['kernel']:>22} {r['shape']:>16} {r['us']:>9.1f}us "
+              f"{r['GB/s']:>7.1f} GB/s  sol={r['sol']:<5}"
+              f" {('%.0f TF/s' % r['TF/s']) if r['TF/s'] else ''}")
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default=None)
+    p.add_argument("--norm-only", action="store_true",
+                   help="stop after the rmsnorm rows")
     args = p.parse_args()
     assert torch.cuda.is_available() and ops.has_hip()
     dev = "cuda"
@@ -68,6 +80,32 @@ def main():
     dy = torch.randn_like(x)
     us = timeit(lambda: ops.ext().rmsnorm_bwd(x, w, dy, inv))
     out.append(row("rmsnorm_bwd", "2048x4096", us, 5 * x.numel() * 2))
+
+    # decode norm, split-K slab variant at the llama2-7b decode shape:
+    # rmsnorm_dec_kernel (default) vs the generic kernel (RB_DEC_NORM=0).
+    # Eager calls of a ~5 us kernel time the host (7 us per call either
+    # way), so each variant is captured as a graph of 50 launches, the way
+    # the engine's decode step replays it, and the replay is timed.
+    xd = torch.randn(32, 4096, dtype=bf16, device=dev)
+    sd = torch.randn(2, 32, 4096, dtype=torch.float32, device=dev)
+    dn_bytes = xd.numel() * 2 * 4 + sd.numel() * 4 + w.numel() * 2
+    graphs = {}
+    for knob in ("1", "0"):
+        os.environ["RB_DEC_NORM"] = knob
+        ops.ext().rmsnorm_res_slab_fwd_dec(xd, sd, w, 1e-5)
+        torch.cuda.synchronize()
+        graphs[knob] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[knob]):
+            for _ in range(50):
+                ops.ext().rmsnorm_res_slab_fwd_dec(xd, sd, w, 1e-5)
+    del os.environ["RB_DEC_NORM"]
+    for knob, name in (("1", "rmsnorm_dec_slab"),
+                       ("0", "rmsnorm_dec_slab_generic")):
+        us = timeit(graphs[knob].replay) / 50
+        out.append(row(name, "32x4096 split2", us, dn_bytes))
+    del graphs
+    if args.norm_only:
+        return report(out, args)
 
     # rope [2048, 32, 128]
     q = torch.randn(2048, 32, 128, dtype=bf16, device=dev)
@@ -308,13 +346,7 @@ def main():
     total = sum(pp.numel() for pp in ps)
     out.append(row("adamw_multi_tensor", "224x64K", us, total * (2 + 2 + 16)))
 
-    for r in out:
-        print(f"{r['kernel']:>22} {r['shape']:>16} {r['us']:>9.1f}us "
-              f"{r['GB/s']:>7.1f} GB/s  sol={r['sol']:<5}"
-              f" {('%.0f TF/s' % r['TF/s']) if r['TF/s'] else ''}")
-    if args.out:
-        with open(args.out, "w") as f:
-            json.dump(out, f, indent=1)
+    report(out, args)
 
 
 if __name__ == "__main__":

@@ -12,6 +12,9 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
+#include <cstdlib>
+#include <cstring>
+
 #include "common.h"
 
 namespace {
@@ -111,6 +114,164 @@ __global__ void rmsnorm_fwd_kernel(const T *__restrict__ x,
     }
     __syncthreads();
   }
+}
+
+// Decode-loop norm (n_rows <= 32, one workgroup per row, grid == n_rows)
+// for D == NV * BLOCK * 8 exactly. The generic kernel above spends its
+// time on dependent memory round trips, not bytes: x, then each slab slice
+// inside a runtime loop, a block reduce, then all of it again plus w. Here
+// NV and the residual MODE are template ints, so every load is an unguarded
+// 16 B load issued before the first use; f is built once and stays in
+// registers across the reduce, and sum_out / y / swz are stored from it.
+//
+// Results are bit-identical to rmsnorm_fwd_kernel<uint16_t>: same fp32 add
+// order (x, then res or slab 0, 1, ...), same per-thread sum-of-squares
+// order (v, then k), same block reduce and rsqrtf expression. The generic
+// kernel's ISA squares with v_pk_mul_f32 and accumulates with v_add_f32 —
+// the compiler did NOT contract `ss += f*f` there — so contraction is
+// switched off for this body to keep each square rounded on its own.
+enum : int { DEC_NONE = 0, DEC_RES = 1, DEC_SLAB2 = 2, DEC_SLAB4 = 4,
+             DEC_SLAB8 = 8 };   // DEC_SLABn: n fp32 split-K slices
+
+typedef __attribute__((ext_vector_type(4))) unsigned int dec_u32x4;
+
+RB_DEV void dec_unpack(const dec_u32x4 &r, float *f) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    f[2 * j] = rb::bf16_to_f32((uint16_t)(r[j] & 0xFFFFu));
+    f[2 * j + 1] = rb::bf16_to_f32((uint16_t)(r[j] >> 16));
+  }
+}
+
+RB_DEV dec_u32x4 dec_pack(const float *f) {
+  dec_u32x4 r;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    r[j] = (uint32_t)rb::f32_to_bf16(f[2 * j]) |
+           ((uint32_t)rb::f32_to_bf16(f[2 * j + 1]) << 16);
+  return r;
+}
+
+template <int NV, int MODE>
+__global__ __launch_bounds__(BLOCK) void rmsnorm_dec_kernel(
+    const uint16_t *__restrict__ x, const uint16_t *__restrict__ res,
+    const float *__restrict__ res32, uint16_t *__restrict__ sum_out,
+    const uint16_t *__restrict__ w, uint16_t *__restrict__ y,
+    uint16_t *__restrict__ swz, int n_rows, int D, float eps) {
+#pragma clang fp contract(off)
+  constexpr int NSL = MODE >= DEC_SLAB2 ? MODE : 0;
+  __shared__ float red[BLOCK / RB_WAVE];
+  const int64_t row = blockIdx.x;
+  const int64_t rowoff = row * D;
+
+  // every load of the row, back to back
+  dec_u32x4 xr[NV], wr[NV], rr[MODE == DEC_RES ? NV : 1];
+  float4 sr[NSL > 0 ? NV : 1][NSL > 0 ? NSL : 1][2];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int col = (v * BLOCK + threadIdx.x) * 8;
+    xr[v] = *reinterpret_cast<const dec_u32x4 *>(x + rowoff + col);
+    if constexpr (MODE == DEC_RES)
+      rr[v] = *reinterpret_cast<const dec_u32x4 *>(res + rowoff + col);
+    if constexpr (NSL > 0) {
+#pragma unroll
+      for (int sl = 0; sl < NSL; ++sl) {
+        const float *rp = res32 + ((int64_t)sl * n_rows + row) * D + col;
+        sr[v][sl][0] = *reinterpret_cast<const float4 *>(rp);
+        sr[v][sl][1] = *reinterpret_cast<const float4 *>(rp + 4);
+      }
+    }
+    wr[v] = *reinterpret_cast<const dec_u32x4 *>(w + col);
+  }
+
+  float f[NV][8];
+  float ss = 0.0f;
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    dec_unpack(xr[v], f[v]);
+    if constexpr (MODE == DEC_RES) {
+      float r[8];
+      dec_unpack(rr[v], r);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) f[v][k] += r[k];
+    }
+    if constexpr (NSL > 0) {
+#pragma unroll
+      for (int sl = 0; sl < NSL; ++sl) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float4 a = sr[v][sl][h];
+          f[v][4 * h] += a.x; f[v][4 * h + 1] += a.y;
+          f[v][4 * h + 2] += a.z; f[v][4 * h + 3] += a.w;
+        }
+      }
+    }
+    if constexpr (MODE != DEC_NONE) {
+      const int col = (v * BLOCK + threadIdx.x) * 8;
+      *reinterpret_cast<dec_u32x4 *>(sum_out + rowoff + col) = dec_pack(f[v]);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ss += f[v][k] * f[v][k];
+  }
+  ss = rb::block_reduce_sum(ss, red);
+  const float ir = rsqrtf(ss / (float)D + eps);
+
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    const int col = (v * BLOCK + threadIdx.x) * 8;
+    float g[8], o[8];
+    dec_unpack(wr[v], g);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = f[v][k] * ir * g[k];
+    const dec_u32x4 p = dec_pack(o);
+    *reinterpret_cast<dec_u32x4 *>(y + rowoff + col) = p;
+    *reinterpret_cast<dec_u32x4 *>(swz + (col >> 4) * 512 +
+                                   ((col >> 3) & 1) * 256 + row * 8) = p;
+  }
+}
+
+// RB_DEC_NORM=0 sends the decode entry points through the generic kernel
+// (A/B switch and test reference). Read per call, like the Python knobs.
+bool dec_norm_enabled() {
+  const char *e = getenv("RB_DEC_NORM");
+  return e == nullptr || strcmp(e, "1") == 0;
+}
+
+template <int NV, int MODE>
+void launch_dec(hipStream_t stream, const uint16_t *x, const uint16_t *res,
+                const float *res32, uint16_t *sum, const uint16_t *w,
+                uint16_t *y, uint16_t *swz, int n_rows, int D, float eps) {
+  hipLaunchKernelGGL((rmsnorm_dec_kernel<NV, MODE>), dim3(n_rows), dim3(BLOCK),
+                     0, stream, x, res, res32, sum, w, y, swz, n_rows, D, eps);
+}
+
+// Launches rmsnorm_dec_kernel when the shape has an instantiation
+// (D in {2048, 4096, 8192}; slab splits 2/4/8) and the knob is on; false
+// means the caller runs the generic kernel.
+bool try_launch_dec(hipStream_t stream, int mode, const uint16_t *x,
+                    const uint16_t *res, const float *res32, uint16_t *sum,
+                    const uint16_t *w, uint16_t *y, uint16_t *swz,
+                    int64_t n_rows, int D, float eps) {
+  if (n_rows < 1 || D % (BLOCK * 8) != 0 || !dec_norm_enabled()) return false;
+  const int nv = D / (BLOCK * 8);
+  if (nv != 1 && nv != 2 && nv != 4) return false;
+  if (mode != DEC_NONE && mode != DEC_RES && mode != DEC_SLAB2 &&
+      mode != DEC_SLAB4 && mode != DEC_SLAB8)
+    return false;
+#define RB_DEC_CASE(NV_, MODE_)                                              \
+  if (nv == NV_ && mode == MODE_) {                                          \
+    launch_dec<NV_, MODE_>(stream, x, res, res32, sum, w, y, swz,            \
+                           (int)n_rows, D, eps);                             \
+    return true;                                                             \
+  }
+#define RB_DEC_MODES(NV_)                                                    \
+  RB_DEC_CASE(NV_, DEC_NONE) RB_DEC_CASE(NV_, DEC_RES)                       \
+  RB_DEC_CASE(NV_, DEC_SLAB2) RB_DEC_CASE(NV_, DEC_SLAB4)                    \
+  RB_DEC_CASE(NV_, DEC_SLAB8)
+  RB_DEC_MODES(1) RB_DEC_MODES(2) RB_DEC_MODES(4)
+#undef RB_DEC_MODES
+#undef RB_DEC_CASE
+  return false;
 }
 
 // Backward: one workgroup per row (grid sized to give every row its own
@@ -296,14 +457,18 @@ std::vector<at::Tensor> rmsnorm_fwd_dec(at::Tensor x, at::Tensor w,
   auto y = at::empty_like(x);
   auto swz = at::empty({(int64_t)(D / 16) * 512}, x.options());
   auto stream = at::cuda::getCurrentHIPStream();
-  auto inv_rms = at::empty({n_rows}, x.options().dtype(at::kFloat));
+  if (try_launch_dec(stream, DEC_NONE, (const uint16_t *)x.data_ptr(), nullptr,
+                     nullptr, nullptr, (const uint16_t *)w.data_ptr(),
+                     (uint16_t *)y.data_ptr(), (uint16_t *)swz.data_ptr(),
+                     n_rows, D, (float)eps))
+    return {y, swz};
   hipLaunchKernelGGL(rmsnorm_fwd_kernel<uint16_t>, dim3(n_rows),
                      dim3(BLOCK), 0, stream,
                      (const uint16_t *)x.data_ptr(),
                      (const uint16_t *)nullptr, (const float *)nullptr, 0,
                      (uint16_t *)nullptr,
                      (const uint16_t *)w.data_ptr(),
-                     (uint16_t *)y.data_ptr(), inv_rms.data_ptr<float>(),
+                     (uint16_t *)y.data_ptr(), (float *)nullptr,
                      (uint16_t *)swz.data_ptr(), n_rows, D, (float)eps);
   return {y, swz};
 }
@@ -325,6 +490,12 @@ std::vector<at::Tensor> rmsnorm_res_fwd_dec(at::Tensor x, at::Tensor res,
   auto y = at::empty_like(x);
   auto swz = at::empty({(int64_t)(D / 16) * 512}, x.options());
   auto stream = at::cuda::getCurrentHIPStream();
+  if (try_launch_dec(stream, DEC_RES, (const uint16_t *)x.data_ptr(),
+                     (const uint16_t *)res.data_ptr(), nullptr,
+                     (uint16_t *)sum.data_ptr(),
+                     (const uint16_t *)w.data_ptr(), (uint16_t *)y.data_ptr(),
+                     (uint16_t *)swz.data_ptr(), n_rows, D, (float)eps))
+    return {sum, y, swz};
   hipLaunchKernelGGL(rmsnorm_fwd_kernel<uint16_t>, dim3(n_rows),
                      dim3(BLOCK), 0, stream,
                      (const uint16_t *)x.data_ptr(),
@@ -355,6 +526,14 @@ std::vector<at::Tensor> rmsnorm_res_slab_fwd_dec(at::Tensor x,
   auto y = at::empty_like(x);
   auto swz = at::empty({(int64_t)(D / 16) * 512}, x.options());
   auto stream = at::cuda::getCurrentHIPStream();
+  const int64_t split = slabs.size(0);
+  if ((split == 2 || split == 4 || split == 8) &&
+      try_launch_dec(stream, (int)split, (const uint16_t *)x.data_ptr(),
+                     nullptr, (const float *)slabs.data_ptr(),
+                     (uint16_t *)sum.data_ptr(),
+                     (const uint16_t *)w.data_ptr(), (uint16_t *)y.data_ptr(),
+                     (uint16_t *)swz.data_ptr(), n_rows, D, (float)eps))
+    return {sum, y, swz};
   hipLaunchKernelGGL(rmsnorm_fwd_kernel<uint16_t>, dim3(n_rows),
                      dim3(BLOCK), 0, stream,
                      (const uint16_t *)x.data_ptr(),

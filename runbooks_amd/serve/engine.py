@@ -652,7 +652,7 @@ class Engine:
         if len(params) == 1 and plain:
             t, p = params.pop()
             toks = ops.sample_tokens(logits, t, top_p=p, seed=seed)
-            out = [int(x) for x in toks]
+            out = toks.tolist()     # one device-to-host copy, not one per row
         else:
             # heterogeneous sampling params / custom seeds: row-by-row
             out = []
