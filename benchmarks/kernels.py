@@ -54,15 +54,60 @@ def report(out, args):
     for r in out:
         print(f"{r['kernel']:>22} {r['shape']:>16} {r['us']:>9.1f}us "
               f"{r['GB/s']:>7.1f} GB/s  sol={r['sol']:<5}"
-              f" {('%.0f TF/s' % r['TF/s']) if r['TF/s'] else ''}")
+              f" {('%.0f TF/s' % r['TF/s']) if r['TF/s'] else ''}"
+              + (f"  F.linear {r['f_linear_bf16_us']:.1f}us ratio "
+                 f"{r['ratio']}" if "ratio" in r else ""))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
 
 
+def w4_gemm_rows(out, dev="cuda"):
+    """csrc/gemm_w4.hip (int4 weight-only, any M) at the llama2-7b
+    projection shapes for prefill-sized M, each against F.linear on the
+    bf16 master (hipBLASLt, what these GEMMs run on without
+    RB_W4_PREFILL / w4_resident) in the same process: the two are timed
+    alternately, three rounds each, and the median round is reported.
+    Three weights per shape are rotated. `ratio` = gemm_w4 / F.linear
+    time (> 1: the int4 GEMM is slower)."""
+    from runbooks_amd.ops.linear import _W4_REGISTRY, quantize_int4
+    bf16 = torch.bfloat16
+    for name, N, K in (("qkv", 12288, 4096), ("o_proj", 4096, 4096),
+                       ("gate_up", 22016, 4096), ("down", 4096, 11008)):
+        ws = [torch.randn(N, K, dtype=bf16, device=dev) * 0.02
+              for _ in range(3)]
+        q4 = [ops.ext().w4_swizzle(*quantize_int4(w)) for w in ws]
+        _W4_REGISTRY.clear()
+        for M in (128, 512, 2048):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            i = [0]
+
+            def g4():
+                i[0] = (i[0] + 1) % 3
+                return ops.ext().gemm_w4(x, *q4[i[0]], N, K)
+
+            def lin():
+                i[0] = (i[0] + 1) % 3
+                return torch.nn.functional.linear(x, ws[i[0]])
+            t4, tl = [], []
+            for _ in range(3):
+                t4.append(timeit(g4, iters=20, warmup=5))
+                tl.append(timeit(lin, iters=20, warmup=5))
+            us, ref = sorted(t4)[1], sorted(tl)[1]
+            r = row(f"gemm_w4 {name}", f"{M}x{N}x{K}", us,
+                    N * K // 2 + N * K // 64 * 2 + (M * K + M * N) * 2,
+                    flops=2 * M * N * K)
+            r["f_linear_bf16_us"] = round(ref, 2)
+            r["ratio"] = round(us / ref, 2)
+            out.append(r)
+        del ws, q4
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default=None)
+    p.add_argument("--w4-gemm-only", action="store_true",
+                   help="only the gemm_w4 vs F.linear rows")
     p.add_argument("--norm-only", action="store_true",
                    help="stop after the rmsnorm rows")
     args = p.parse_args()
@@ -70,6 +115,9 @@ def main():
     dev = "cuda"
     bf16 = torch.bfloat16
     out = []
+    if args.w4_gemm_only:
+        w4_gemm_rows(out, dev)
+        return report(out, args)
 
     # rmsnorm fwd/bwd [2048, 4096]
     x = torch.randn(2048, 4096, dtype=bf16, device=dev)
@@ -307,6 +355,8 @@ def main():
                        N * K // 2 + N * K // 64 * 2,
                        flops=2 * 32 * N * K))
         del q4
+
+    w4_gemm_rows(out, dev)
 
     # fp8 decode GEMM
     from runbooks_amd.ops.linear import quantize_fp8

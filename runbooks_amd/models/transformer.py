@@ -532,15 +532,82 @@ class Transformer(nn.Module):
                 for _ in range(self.cfg.num_layers)]
 
 
+def release_w4_masters(model: "Transformer") -> int:
+    """Int4-resident serving: free the bf16 master of every weight that
+    has an int4 registration (fused qkv, fused gate-up, o_proj, down_proj,
+    an untied lm_head) together with the per-projection view Parameters
+    that keep a fused storage alive. Each becomes a meta-device
+    placeholder of the same shape and dtype that carries the int4
+    registration (ops/linear.py _W4_RELEASED); every GEMM on it then runs
+    csrc/decode_gemm_w4.hip (M <= 32) or csrc/gemm_w4.hip, and anything
+    that would read the master raises a RuntimeError naming the weight. A
+    tied lm_head/embedding keeps its master: the embedding gather reads
+    it. Returns the bytes released."""
+    from ..ops.linear import release_w4_placeholder, w4_registered
+    released = 0
+    first = []
+
+    def swap(owner, attr, name, view=False):
+        nonlocal released
+        w = getattr(owner, attr)
+        ph = release_w4_placeholder(w, name, view=view)
+        setattr(owner, attr, ph)
+        first.append(ph)
+        if not view:
+            released += w.numel() * w.element_size()
+
+    for i, blk in enumerate(model.blocks):
+        attn, mlp = blk.attn, blk.mlp
+        w = getattr(attn, "_qkv_w", None)
+        if w is not None and w4_registered(w):
+            swap(attn, "_qkv_w", f"blocks.{i}.attn.qkv (fused)")
+            for proj in ("q_proj", "k_proj", "v_proj"):
+                swap(getattr(attn, proj), "weight",
+                     f"blocks.{i}.attn.{proj}.weight", view=True)
+        w = getattr(mlp, "_gateup_w", None)
+        if w is not None and w4_registered(w):
+            swap(mlp, "_gateup_w", f"blocks.{i}.mlp.gate_up (fused)")
+            for proj in ("gate_proj", "up_proj"):
+                swap(getattr(mlp, proj), "weight",
+                     f"blocks.{i}.mlp.{proj}.weight", view=True)
+        if w4_registered(attn.o_proj.weight):
+            swap(attn.o_proj, "weight", f"blocks.{i}.attn.o_proj.weight")
+        if w4_registered(mlp.down_proj.weight):
+            swap(mlp.down_proj, "weight", f"blocks.{i}.mlp.down_proj.weight")
+    if model.lm_head.weight is not model.embed.weight and \
+            w4_registered(model.lm_head.weight):
+        swap(model.lm_head, "weight", "lm_head.weight")
+
+    if first:
+        from ..ops.linear import _check_master
+
+        def refuse_state_dict(module, prefix, keep_vars):
+            _check_master(first[0], "state_dict() / checkpoint save")
+
+        model.register_state_dict_pre_hook(refuse_state_dict)
+        model._w4_resident = True
+        if torch.cuda.is_available():
+            # hand the freed blocks back so the engine's KV-pool sizing
+            # sees them as free memory
+            torch.cuda.empty_cache()
+    return released
+
+
 def fuse_for_inference(model: "Transformer",
                        load_in_8bit: bool = False,
-                       load_in_4bit: bool = False) -> "Transformer":
+                       load_in_4bit: bool = False,
+                       w4_resident: bool = False) -> "Transformer":
     """Fuse each block's QKV and gate/up weights into single tensors for
     serving: one wide GEMM per group instead of 2-3 skinny ones (the
     batch-<=32 decode GEMMs are weight-bandwidth bound, and hipBLASLt is
     markedly more efficient at the fused N — profiles/). The original
     parameters become views into the fused tensor, so no extra HBM and
     the separate-projection training path keeps working.
+
+    ``w4_resident`` (with ``load_in_4bit``, on a GPU) drops the bf16
+    masters of the int4-quantized weights afterwards
+    (release_w4_masters): the model then serves from its int4 copies
+    alone and can no longer train or save a checkpoint.
     """
     for blk in model.blocks:
         attn = blk.attn
@@ -643,7 +710,9 @@ def fuse_for_inference(model: "Transformer",
         # MODEL_LOAD_IN_4BIT: the same decode weight set additionally
         # stored as group-64 int4 + bf16 scales (4.25 bits/weight) for
         # ops/csrc/decode_gemm_w4.hip. bf16 masters stay for prefill and
-        # m > 32, the same both-copies trade as the fp8 branch.
+        # m > 32, the same both-copies trade as the fp8 branch, unless
+        # w4_resident drops them: m > 32 then runs ops/csrc/gemm_w4.hip
+        # on the same int4 copy.
         from ..ops.linear import quantize_int4
         ext = ops.ext()
         for blk in model.blocks:
@@ -657,6 +726,8 @@ def fuse_for_inference(model: "Transformer",
         if ext.decode_gemm_w4_supported(32, model.lm_head.weight.shape[0],
                                         model.lm_head.weight.shape[1]):
             quantize_int4(model.lm_head.weight)
+        if w4_resident:
+            release_w4_masters(model)
     return model
 
 

@@ -15,7 +15,7 @@ from .attention import (causal_attention, flash_prefill, paged_decode,  # noqa: 
 from .kvcache import BLOCK_SIZE, alloc_kv_cache, kv_append, kv_append_ref  # noqa: F401
 from .linear import (Linear, decode_layout, decode_linear_glu,  # noqa: F401
                      decode_linear_raw, decode_linear_rope_append,
-                     fast_linear, fused_epilogue_ok)
+                     fast_linear, fused_epilogue_ok, w4_prefill_enabled)
 from .norm import RMSNorm, rmsnorm, rmsnorm_ref  # noqa: F401
 from .rope import rope, rope_ref, rope_tables  # noqa: F401
 from .sampling import sample_tokens  # noqa: F401

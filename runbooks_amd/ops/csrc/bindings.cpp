@@ -81,6 +81,9 @@ at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
                           int64_t M, int64_t N, int64_t K, int64_t force_split);
 int64_t decode_gemm_w4_split(int64_t N, int64_t K);
 bool decode_gemm_w4_supported(int64_t M, int64_t N, int64_t K);
+at::Tensor gemm_w4(at::Tensor x, at::Tensor wq_swz, at::Tensor sc_swz,
+                   int64_t N, int64_t K);
+bool gemm_w4_supported(int64_t M, int64_t N, int64_t K);
 int64_t skinny_gemm_mmax();
 at::Tensor qkv_rope_append(at::Tensor y, at::Tensor cos, at::Tensor sin,
                            at::Tensor positions, at::Tensor k_cache,
@@ -196,6 +199,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("N"), py::arg("K"), py::arg("force_split") = -1);
   m.def("decode_gemm_w4_split", &decode_gemm_w4_split);
   m.def("decode_gemm_w4_supported", &decode_gemm_w4_supported);
+  m.def("gemm_w4", &gemm_w4,
+        "int4 weight-only MFMA GEMM, any M, over the decode kernel's stored "
+        "copy: y[M,N] = x[M,K] @ dequant(Wq)^T (bf16)",
+        py::arg("x"), py::arg("wq_swz"), py::arg("sc_swz"), py::arg("N"),
+        py::arg("K"));
+  m.def("gemm_w4_supported", &gemm_w4_supported);
   m.def("qkv_rope_append", &qkv_rope_append,
         "packed qkv -> rope'd q + rope'd k / v appended to the paged cache");
   m.def("swiglu_packed", &swiglu_packed,

@@ -49,6 +49,7 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "w4_dequant.h"
 
 namespace {
 
@@ -66,34 +67,8 @@ __device__ __forceinline__ bf16x8v load8v(const uint16_t *p) {
   return c.v;
 }
 
-// byte b of `bytes` (a nibble value n = 0..15) -> the f32 128 + n, built
-// by one byte permute: 0x43000000 is 128.0f and mantissa bit 16 weighs 1,
-// so dropping n into byte 2 adds exactly n. (Byte selector: 7 = byte 3 of
-// the first operand, b = byte b of the second, 0x0C = constant zero.)
-template <int B>
-__device__ __forceinline__ float w4_byte_to_f32(uint32_t bytes) {
-  union { uint32_t u; float f; } c;
-  c.u = __builtin_amdgcn_perm(0x43000000u, bytes, 0x07000C0Cu | (B << 16));
-  return c.f;
-}
-
-// 8 nibbles of one dword -> 8 bf16 A-fragment elements; nb = -136 * s, so
-// fma(128 + n, s, nb) == (n - 8) * s exactly (every term fits 16 bits).
-__device__ __forceinline__ bf16x8v w4_dequant8(uint32_t w, float s,
-                                               float nb) {
-  const uint32_t even = w & 0x0F0F0F0Fu;          // nibbles 0,2,4,6
-  const uint32_t odd = (w >> 4) & 0x0F0F0F0Fu;    // nibbles 1,3,5,7
-  bf16x8v v;
-  v[0] = (__bf16)__builtin_fmaf(w4_byte_to_f32<0>(even), s, nb);
-  v[1] = (__bf16)__builtin_fmaf(w4_byte_to_f32<0>(odd), s, nb);
-  v[2] = (__bf16)__builtin_fmaf(w4_byte_to_f32<1>(even), s, nb);
-  v[3] = (__bf16)__builtin_fmaf(w4_byte_to_f32<1>(odd), s, nb);
-  v[4] = (__bf16)__builtin_fmaf(w4_byte_to_f32<2>(even), s, nb);
-  v[5] = (__bf16)__builtin_fmaf(w4_byte_to_f32<2>(odd), s, nb);
-  v[6] = (__bf16)__builtin_fmaf(w4_byte_to_f32<3>(even), s, nb);
-  v[7] = (__bf16)__builtin_fmaf(w4_byte_to_f32<3>(odd), s, nb);
-  return v;
-}
+// w4_byte_to_f32 / w4_dequant8: w4_dequant.h (shared with gemm_w4.hip).
+using rb::w4_dequant8;
 
 // One ring half = U groups: raw weight bytes (nontemporal: streamed once,
 // must not evict L2), raw scale, and the 4 x fragments per group (plain

@@ -56,6 +56,8 @@ def fused_epilogue_enabled() -> bool:
 
 
 def _registry_get(reg: dict, weight: torch.Tensor):
+    if weight.device.type == "meta":     # released master: no storage to key
+        return None
     entry = reg.get(weight.data_ptr())
     if entry is None:
         return None
@@ -70,6 +72,7 @@ def register_decode_weight(weight: torch.Tensor, layout: str = "plain",
     """Build + register the decode-GEMM weight layout for `weight`.
     `layout` "glu16" needs a fused gate-up [2I, K] with I % 16 == 0;
     "rope16" a fused qkv [(hq + 2*hkv) * dh, K] with (dh/2) % 16 == 0."""
+    _check_master(weight, "the RB_DECODE_GEMM registration")
     for ptr in [p for p, e in _DECODE_W_REGISTRY.items() if e[-1]() is None]:
         del _DECODE_W_REGISTRY[ptr]          # purge dead entries
     if layout == "rope16":
@@ -112,6 +115,95 @@ def dequantize_fp8(w8_bytes: torch.Tensor, scale: torch.Tensor,
 _W4_REGISTRY: dict[int, tuple] = {}
 
 W4_GROUP = 64
+
+# id(placeholder) -> (wq_swz, sc_swz, (N, K), name, weakref to the
+# placeholder): weights whose bf16 master release_w4_masters freed (int4-
+# resident serving). The placeholder is a meta-device tensor of the
+# master's shape and dtype, so it has no data_ptr to key on: these entries
+# are keyed on object identity, verified through the weakref like the
+# others. wq_swz / sc_swz are None for a released VIEW of a fused weight
+# (q_proj.weight ...), which has no int4 copy of its own.
+_W4_RELEASED: dict[int, tuple] = {}
+
+
+def w4_prefill_enabled() -> bool:
+    """RB_W4_PREFILL=1 sends M > 32 GEMMs on an int4-registered weight to
+    csrc/gemm_w4.hip instead of F.linear on the bf16 master. Off by
+    default; forced on while an int4-resident model is alive (its masters
+    are gone)."""
+    if os.environ.get("RB_W4_PREFILL", "0") == "1":
+        return True
+    if _W4_RELEASED:
+        _purge_released()
+    return bool(_W4_RELEASED)
+
+
+def _released_get(weight: torch.Tensor):
+    entry = _W4_RELEASED.get(id(weight))
+    if entry is None or entry[-1]() is not weight:
+        return None
+    return entry
+
+
+def _check_master(weight: torch.Tensor, what: str) -> None:
+    """Raise instead of reading a released (placeholder) master."""
+    if weight.device.type != "meta":
+        return
+    entry = _released_get(weight)
+    name = entry[3] if entry is not None else "<unnamed>"
+    raise RuntimeError(
+        f"weight {name} {tuple(weight.shape)}: the model is int4-resident "
+        f"(w4_resident), its bf16 master was released and {what} needs it. "
+        "Only bf16, bias-free, no-grad inference runs on an int4-resident "
+        "model")
+
+
+def _w4_get(weight: torch.Tensor):
+    """(wq_swz, sc_swz, (N, K), ...) of an int4-registered weight, released
+    or not; None without one."""
+    if weight.device.type == "meta":
+        entry = _released_get(weight)
+        return entry if entry is not None and entry[0] is not None else None
+    if not _W4_REGISTRY:
+        return None
+    return _registry_get(_W4_REGISTRY, weight)
+
+
+def _purge_released() -> None:
+    for key in [k for k, e in _W4_RELEASED.items() if e[-1]() is None]:
+        del _W4_RELEASED[key]
+
+
+def w4_registered(weight: torch.Tensor) -> bool:
+    """True when `weight` (released or not) has an int4 kernel copy."""
+    return _w4_get(weight) is not None
+
+
+def release_w4_placeholder(weight: torch.Tensor, name: str,
+                           view: bool = False) -> torch.Tensor:
+    """Meta-device stand-in for `weight` (same shape and dtype, no
+    storage). The int4 registration of `weight` moves to the placeholder,
+    keyed on identity; `view` marks a per-projection view of a fused
+    weight, which has none of its own (and shares the fused weight's
+    data_ptr, so it is not looked up). The caller swaps the placeholder in
+    for every reference to `weight`; the master is freed when the last one
+    goes."""
+    _purge_released()
+    entry = None if view else _registry_get(_W4_REGISTRY, weight)
+    if entry is None and not view:
+        raise RuntimeError(f"release_w4_placeholder: {name} has no int4 "
+                           "registration")
+    ph = torch.empty(weight.shape, dtype=weight.dtype, device="meta")
+    if isinstance(weight, torch.nn.Parameter):
+        ph = torch.nn.Parameter(ph, requires_grad=False)
+    if entry is not None:
+        del _W4_REGISTRY[weight.data_ptr()]
+        _W4_RELEASED[id(ph)] = (entry[0], entry[1], entry[2], name,
+                                weakref.ref(ph))
+    else:
+        _W4_RELEASED[id(ph)] = (None, None, tuple(weight.shape), name,
+                                weakref.ref(ph))
+    return ph
 
 
 def _w4_codes(weight: torch.Tensor):
@@ -178,8 +270,18 @@ def fake_quantize_int4_(weight: torch.Tensor) -> torch.Tensor:
     return weight
 
 
+def gemm_w4(x: torch.Tensor, q4) -> torch.Tensor:
+    """x [..., K] bf16 @ dequant(int4 entry q4)^T through csrc/gemm_w4.hip
+    (any M; fast_linear uses it for M > 32)."""
+    n, k = q4[2]
+    y = _backend.ext().gemm_w4(x.reshape(-1, k).contiguous(), q4[0], q4[1],
+                               n, k)
+    return y.view(*x.shape[:-1], n)
+
+
 def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                 bias: torch.Tensor | None = None) -> torch.Tensor:
+    released = weight.device.type == "meta"
     if (bias is None and not torch.is_grad_enabled()
             and x.dtype == torch.bfloat16 and _backend.use_hip(x)
             and weight.is_contiguous()):
@@ -187,8 +289,8 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
         m = x.numel() // k
         n = weight.shape[0]
         if m <= 32:
-            if _W4_REGISTRY:
-                q4 = _registry_get(_W4_REGISTRY, weight)
+            if _W4_REGISTRY or released:
+                q4 = _w4_get(weight)
                 if q4 is not None and \
                         _backend.ext().decode_gemm_w4_supported(m, n, k):
                     # same operand contract as the bf16 v2 branch below
@@ -199,6 +301,8 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                     y = _backend.ext().decode_gemm_w4(xs, q4[0], q4[1],
                                                       m, n, k)
                     return y.view(*x.shape[:-1], n)
+            if released:
+                _check_master(weight, "a GEMM without an int4 kernel")
             if n % 64 == 0 and k % 256 == 0:
                 q = _registry_get(_FP8_REGISTRY, weight)
                 if q is not None:
@@ -223,6 +327,15 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                 y = _backend.ext().skinny_gemm(x.reshape(m, k).contiguous(),
                                                weight)
                 return y.view(*x.shape[:-1], n)
+        elif (_W4_REGISTRY or released) and w4_prefill_enabled():
+            # int4 weight-only GEMM at large M: prefill, chunked and
+            # batched prefill multiply by the weights decode streams
+            q4 = _w4_get(weight)
+            if q4 is not None and _backend.ext().gemm_w4_supported(m, n, k):
+                return gemm_w4(x, q4)
+    if released:
+        _check_master(weight, "the F.linear path (non-bf16 input, bias, "
+                      "grad enabled or CPU input)")
     return F.linear(x, weight, bias)
 
 

@@ -119,7 +119,8 @@ class Engine:
                  kv_fp8: bool | None = None, load_in_4bit: bool = False,
                  prefill_from_cache: bool | None = None,
                  prefill_chunk: int | None = None,
-                 prefill_batch: int | None = None):
+                 prefill_batch: int | None = None,
+                 w4_resident: bool | None = None):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
@@ -130,6 +131,24 @@ class Engine:
             print("engine: MODEL_LOAD_IN_4BIT and MODEL_LOAD_IN_8BIT both "
                   "set; serving 4-bit", flush=True)
             load_in_8bit = False
+        # Int4-resident serving (RB_W4_RESIDENT=1 or w4_resident=True, with
+        # load_in_4bit): the bf16 masters of the int4-quantized weights
+        # are freed right after quantization, BEFORE the KV pool is sized
+        # below, so the freed bytes become KV blocks; prefill then runs
+        # the int4 GEMM (ops/csrc/gemm_w4.hip) on the weights decode
+        # streams.
+        import os as _os1
+        if w4_resident is None:
+            w4_resident = _os1.environ.get("RB_W4_RESIDENT", "0") == "1"
+        if w4_resident and not (torch.cuda.is_available() and load_in_4bit
+                                and model.tp == 1):
+            print("engine: w4_resident ignored "
+                  + ("without a GPU" if not torch.cuda.is_available()
+                     else "at TP>1" if model.tp > 1
+                     else "without load_in_4bit")
+                  + " (the bf16 master weights stay)", flush=True)
+            w4_resident = False
+        self.w4_resident = bool(w4_resident)
         if torch.cuda.is_available():
             # TP>1 included: each rank fuses ITS OWN qkv / gate-up weight
             # shards and registers decode-GEMM layouts for them — the
@@ -138,7 +157,8 @@ class Engine:
             from ..models.transformer import fuse_for_inference
             fuse_for_inference(self.model,
                                load_in_8bit=load_in_8bit and model.tp == 1,
-                               load_in_4bit=load_in_4bit and model.tp == 1)
+                               load_in_4bit=load_in_4bit and model.tp == 1,
+                               w4_resident=self.w4_resident)
         if load_in_4bit and model.tp > 1:
             print("engine: MODEL_LOAD_IN_4BIT ignored at TP>1 "
                   "(int4 decode path is single-GPU, like the fp8 one)",

@@ -11,6 +11,9 @@ examples/llama2-7b/server.yaml, container-contract.md:50-56) — loads
   4-bit stores group-64 int4 + bf16 scales; both keep the bf16 masters
   for prefill. 4-bit wins when both are set; both apply at TP=1 on a GPU
   and are otherwise ignored (bf16 serving).
+- PARAM_W4_RESIDENT / W4_RESIDENT ("1" or "true", with MODEL_LOAD_IN_4BIT):
+  drop the bf16 masters of the 4-bit weights; prefill runs the int4 GEMM
+  and the freed memory becomes KV cache.
 - TP: tensor parallelism degree (defaults to visible GPU count); ranks
   are spawned via torch.distributed.run over RCCL/xGMI.
 """
@@ -103,8 +106,13 @@ def main():
     # prefill forward per engine step (0, 1 or unset = one forward each)
     pbatch = int(os.environ.get("PARAM_PREFILL_BATCH",
                                 os.environ.get("PREFILL_BATCH", "")) or 0)
+    # PARAM_W4_RESIDENT / W4_RESIDENT: serve a 4-bit model from its int4
+    # weights alone (no bf16 masters)
+    resident = os.environ.get(
+        "PARAM_W4_RESIDENT",
+        os.environ.get("W4_RESIDENT", "")).lower() in ("1", "true")
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
-                    kv_fp8=kv_fp8,
+                    kv_fp8=kv_fp8, w4_resident=resident or None,
                     # unset leaves the engine's own RB_* env defaults
                     prefill_from_cache=from_cache or None,
                     prefill_chunk=chunk or None,
