@@ -190,6 +190,16 @@ def main():
     out.append(row("cross_entropy_fwd+bwd", "2048x32000", us,
                    3 * logits.numel() * 2))
 
+    # batched per-request sampler [32, 32000]: top-p 0.9 on every row and
+    # 5 logprobs; bytes = one read of the logits + the fp32 workspace
+    # written once (its re-reads stay in L2)
+    slog = torch.randn(32, 32000, device=dev).mul_(4).to(bf16)
+    sparams, _ = ops.pack_sample_batch(
+        [dict(temperature=0.8, top_p=0.9, seed=i) for i in range(32)])
+    us = timeit(lambda: ops.sample_batch(slog, sparams, None, 5))
+    out.append(row("sample_batch top_p L=5", "32x32000", us,
+                   slog.numel() * (2 + 4)))
+
     # flash prefill / training fwd [4, 512, 32, 128]
     qq = torch.randn(4, 512, 32, 128, dtype=bf16, device=dev)
     kk, vv = torch.randn_like(qq), torch.randn_like(qq)

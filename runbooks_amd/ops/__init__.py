@@ -18,4 +18,5 @@ from .linear import (Linear, decode_layout, decode_linear_glu,  # noqa: F401
                      fast_linear, fused_epilogue_ok, w4_prefill_enabled)
 from .norm import RMSNorm, rmsnorm, rmsnorm_ref  # noqa: F401
 from .rope import rope, rope_ref, rope_tables  # noqa: F401
-from .sampling import sample_tokens  # noqa: F401
+from .sampling import (SampleBatchResult, pack_sample_batch,  # noqa: F401
+                       sample_batch, sample_batch_ref, sample_tokens)

@@ -35,6 +35,8 @@ void adamw_step_multi(at::Tensor table, int64_t nchunks, bool p32, bool g32,
                       double wd, int64_t step);
 int64_t adamw_mt_chunk_elems();
 at::Tensor sample_tokens(at::Tensor logits, double temperature, int64_t seed);
+at::Tensor sample_batch(at::Tensor logits, at::Tensor params_cpu,
+                        c10::optional<at::Tensor> pen_cpu, int64_t num_logprobs);
 void kv_append(at::Tensor k, at::Tensor v, at::Tensor k_cache, at::Tensor v_cache,
                at::Tensor slot_mapping);
 at::Tensor paged_decode(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
@@ -136,6 +138,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adamw_mt_chunk_elems", &adamw_mt_chunk_elems,
         "elements per multi-tensor chunk");
   m.def("sample_tokens", &sample_tokens, "greedy / Gumbel-max sampling");
+  m.def("sample_batch", &sample_batch,
+        "batched per-row sampler: penalties, top-k/top-p/min-p, draw, "
+        "logprobs -> packed int32 [B, 4 + 2L]",
+        py::arg("logits"), py::arg("params_cpu"),
+        py::arg("pen_cpu") = py::none(), py::arg("num_logprobs") = 0);
   m.def("kv_append", &kv_append, "paged KV-cache append");
   m.def("paged_decode", &paged_decode, "paged GQA/MQA decode attention",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),

@@ -13,25 +13,13 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "sampling_rng.h"
 
 namespace {
 
 constexpr int BLOCK = 256;
 
-RB_DEV uint32_t hash_u32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU;
-  x ^= x >> 15; x *= 0x846ca68bU;
-  x ^= x >> 16;
-  return x;
-}
-
-// uniform in (0, 1]
-RB_DEV float rng_uniform(uint64_t seed, uint32_t row, uint32_t col) {
-  uint32_t h = hash_u32((uint32_t)seed ^ hash_u32(row * 0x9e3779b9U ^ hash_u32(col)));
-  h ^= (uint32_t)(seed >> 32);
-  h = hash_u32(h);
-  return ((float)h + 1.0f) * (1.0f / 4294967296.0f);
-}
+using rb::rng_uniform;
 
 template <typename T, bool GUMBEL>
 __global__ void sample_kernel(const T *__restrict__ logits,
@@ -57,7 +45,7 @@ __global__ void sample_kernel(const T *__restrict__ logits,
         const int idx = i * W + k;
         if (GUMBEL) {
           const float u = rng_uniform(seed, (uint32_t)row, (uint32_t)idx);
-          v = v * inv_temp - __logf(-__logf(u));
+          v = v * inv_temp - rb::neg_gumbel(u);
         }
         if (v > best) { best = v; best_i = idx; }
       }
@@ -66,7 +54,7 @@ __global__ void sample_kernel(const T *__restrict__ logits,
       float v = rb::bf16_to_f32_or_id(lr[i]);
       if (GUMBEL) {
         const float u = rng_uniform(seed, (uint32_t)row, (uint32_t)i);
-        v = v * inv_temp - __logf(-__logf(u));
+        v = v * inv_temp - rb::neg_gumbel(u);
       }
       if (v > best) { best = v; best_i = i; }
     }

@@ -92,6 +92,8 @@ class Request:
     frequency_penalty: float = 0.0  # subtract per occurrence
     repetition_penalty: float = 1.0  # HF-style multiplicative penalty
     stop_ids: tuple[int, ...] = ()
+    top_k: int = 0                  # keep the k most likely tokens (0 = off)
+    min_p: float = 0.0              # keep p >= min_p * p_max (0 = off)
     # state
     output_ids: list[int] = field(default_factory=list)
     # per output token, when logprobs is set: {"logprob": f, "top": [(id, f)]}
@@ -120,7 +122,8 @@ class Engine:
                  prefill_from_cache: bool | None = None,
                  prefill_chunk: int | None = None,
                  prefill_batch: int | None = None,
-                 w4_resident: bool | None = None):
+                 w4_resident: bool | None = None,
+                 batch_sampler: bool | None = None):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
@@ -284,12 +287,25 @@ class Engine:
                   + " (paged prefill is single-GPU bf16; one prefill per "
                   "request is used)", flush=True)
             self.prefill_batch = 0
+        # Batched sampler (off by default): RB_BATCH_SAMPLER=1 /
+        # batch_sampler=True samples every batch, whatever mix of
+        # per-request parameters it holds, with one ops.sample_batch call
+        # and one download (ops/csrc/sample_batch.hip). A batch in which a
+        # request sets top_k or min_p takes that path whatever the knob
+        # says: the older path has no such filters.
+        self.batch_sampler = (
+            batch_sampler if batch_sampler is not None
+            else _os.environ.get("RB_BATCH_SAMPLER", "0") == "1")
+        # request_id -> {token id: count} over prompt + output, kept up to
+        # date one token at a time for the batched sampler's penalty CSR
+        self._tok_counts: dict[int, dict] = {}
         self.stats = {"steps": 0, "prefills": 0, "decode_tokens": 0,
                       "preemptions": 0, "prefix_hits": 0,
                       "prefix_hit_blocks": 0, "window_dropped_blocks": 0,
                       "prefill_tokens": 0, "prefix_skipped_tokens": 0,
                       "prefill_chunks": 0, "prefill_batches": 0,
-                      "prefill_batched_requests": 0}
+                      "prefill_batched_requests": 0,
+                      "sampler_batched_steps": 0}
 
     def _auto_kv_blocks(self, mem_fraction: float) -> int:
         elem = (self.cfg.head_dim + 16) if self.kv_fp8 \
@@ -310,11 +326,13 @@ class Engine:
                presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0,
                repetition_penalty: float = 1.0,
-               stop_token_ids: tuple[int, ...] = ()) -> Request:
+               stop_token_ids: tuple[int, ...] = (),
+               top_k: int = 0, min_p: float = 0.0) -> Request:
         req = Request(self._next_id, list(prompt_ids), max_new_tokens,
                       temperature, top_p, logprobs, seed,
                       presence_penalty, frequency_penalty,
-                      repetition_penalty, tuple(stop_token_ids))
+                      repetition_penalty, tuple(stop_token_ids),
+                      int(top_k or 0), float(min_p or 0.0))
         self._next_id += 1
         self.waiting.append(req)
         return req
@@ -445,6 +463,8 @@ class Engine:
 
     def _sample_first(self, req: Request, logits) -> int:
         """Sample the first output token from last-position prefill logits."""
+        if self._use_batch_sampler([req]):
+            return self._sample_batched(logits[:1], [req])[0]
         S = len(req.prompt_ids)
         # a per-request seed makes sampling reproducible across runs and
         # independent of the request_id the scheduler happened to assign
@@ -663,7 +683,69 @@ class Engine:
                                        bt, seq_lens, seq_starts=start_t)
         return self._sample_batch(logits, reqs)
 
+    def _use_batch_sampler(self, reqs: list[Request]) -> bool:
+        return self.batch_sampler or any(r.top_k > 0 or r.min_p > 0.0
+                                         for r in reqs)
+
+    def _token_counts(self, r: Request) -> dict:
+        """{token id: count} over the request's prompt + output. Counted
+        once, then one token per step; recounted when the sequence is not
+        the counted one plus new output (preemption folds the output into
+        the prompt)."""
+        ent = self._tok_counts.get(r.request_id)
+        n_p, n_o = len(r.prompt_ids), len(r.output_ids)
+        if ent is None or ent["prompt"] != n_p or ent["out"] > n_o:
+            cnt: dict[int, int] = {}
+            for t in r.prompt_ids:
+                cnt[t] = cnt.get(t, 0) + 1
+            ent = {"prompt": n_p, "out": 0, "cnt": cnt}
+            self._tok_counts[r.request_id] = ent
+        cnt = ent["cnt"]
+        for t in r.output_ids[ent["out"]:]:
+            cnt[t] = cnt.get(t, 0) + 1
+        ent["out"] = n_o
+        return cnt
+
+    def _sample_batched(self, logits, reqs: list[Request]) -> list[int]:
+        """One ops.sample_batch call and one download for the whole
+        batch, each row with its own parameters and seed."""
+        rows, counts = [], []
+        for r in reqs:
+            base = (r.seed * 2654435761 if r.seed is not None
+                    else self.seed + r.request_id * 65537)
+            rows.append({"temperature": r.temperature, "top_k": r.top_k,
+                         "top_p": r.top_p, "min_p": r.min_p,
+                         "presence": r.presence_penalty,
+                         "frequency": r.frequency_penalty,
+                         "repetition": r.repetition_penalty,
+                         "seed": base + r.seq_len})
+            pen = (r.presence_penalty or r.frequency_penalty
+                   or r.repetition_penalty != 1.0)
+            counts.append(self._token_counts(r) if pen else None)
+        want = [r.logprobs for r in reqs if r.logprobs is not None]
+        V = logits.shape[-1]
+        L = min(max(want, default=0), ops.sampling.MAX_LOGPROBS, V)
+        params, penalties = ops.pack_sample_batch(rows, counts)
+        res = ops.sample_batch(logits.reshape(-1, V).contiguous(), params,
+                               penalties, num_logprobs=L).host()
+        out = res.tokens.tolist()
+        self.stats["sampler_batched_steps"] += 1
+        if want:
+            lps = res.logprobs.tolist()
+            ids, tops = res.top_ids.tolist(), res.top_logprobs.tolist()
+            for i, r in enumerate(reqs):
+                if r.logprobs is None:
+                    continue
+                entry = {"logprob": lps[i]}
+                k = min(r.logprobs or 0, L)
+                if k > 0:
+                    entry["top"] = list(zip(ids[i][:k], tops[i][:k]))
+                r.logprob_data.append(entry)
+        return out
+
     def _sample_batch(self, logits, reqs: list[Request]) -> list[int]:
+        if self._use_batch_sampler(reqs):
+            return self._sample_batched(logits, reqs)
         seed = self.seed + 1_000_003 * reqs[0].seq_len
         params = {(r.temperature, r.top_p) for r in reqs}
         plain = all(r.seed is None and not r.presence_penalty and
@@ -885,6 +967,7 @@ class Engine:
                 self.allocator.release(r.blocks)
                 r.blocks = []
                 self.running.remove(r)
+                self._tok_counts.pop(r.request_id, None)
                 finished.append(r)
 
     def has_work(self) -> bool:

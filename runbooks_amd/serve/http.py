@@ -63,6 +63,8 @@ class CompletionRequest(BaseModel):
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     repetition_penalty: float = 1.0
+    top_k: int = 0               # keep the k most likely tokens (0 = off)
+    min_p: float = 0.0           # keep p >= min_p * p_max (0 = off)
     stop: list[str] | str | None = None
     model: str = ""
     stream: bool = False
@@ -88,6 +90,8 @@ class ChatRequest(BaseModel):
     presence_penalty: float = 0.0
     frequency_penalty: float = 0.0
     repetition_penalty: float = 1.0
+    top_k: int = 0               # keep the k most likely tokens (0 = off)
+    min_p: float = 0.0           # keep p >= min_p * p_max (0 = off)
     stop: list[str] | str | None = None
     model: str = ""
     stream: bool = False
@@ -110,7 +114,8 @@ class EngineLoop:
                top_p=1.0, logprobs=None, seed=None,
                presence_penalty=0.0, frequency_penalty=0.0,
                repetition_penalty=1.0,
-               stop_token_ids=()) -> tuple[queue.Queue, "object"]:
+               stop_token_ids=(), top_k=0,
+               min_p=0.0) -> tuple[queue.Queue, "object"]:
         """Returns (queue yielding token_id | None, engine Request)."""
         q: queue.Queue = queue.Queue()
         with self._lock:
@@ -120,7 +125,8 @@ class EngineLoop:
                                      presence_penalty=presence_penalty,
                                      frequency_penalty=frequency_penalty,
                                      repetition_penalty=repetition_penalty,
-                                     stop_token_ids=stop_token_ids)
+                                     stop_token_ids=stop_token_ids,
+                                     top_k=top_k, min_p=min_p)
             self._watchers[req.request_id] = q
             req._watch_sent = 0
         self._wake.set()
@@ -387,7 +393,8 @@ def build_app(engine: Engine, tokenizer=None,
                             presence_penalty=req.presence_penalty,
                             frequency_penalty=req.frequency_penalty,
                             repetition_penalty=req.repetition_penalty,
-                            stop_token_ids=eos_ids)
+                            stop_token_ids=eos_ids,
+                            top_k=req.top_k, min_p=req.min_p)
                 for i in range(n_sample)]
         q, ereq = subs[0]
 
@@ -483,7 +490,8 @@ def build_app(engine: Engine, tokenizer=None,
                                   presence_penalty=req.presence_penalty,
                                   frequency_penalty=req.frequency_penalty,
                                   repetition_penalty=req.repetition_penalty,
-                                  stop_token_ids=eos_ids)
+                                  stop_token_ids=eos_ids,
+                                  top_k=req.top_k, min_p=req.min_p)
 
             def gen():
                 def chunk(delta):
@@ -513,6 +521,7 @@ def build_app(engine: Engine, tokenizer=None,
             seed=req.seed, presence_penalty=req.presence_penalty,
             frequency_penalty=req.frequency_penalty,
             repetition_penalty=req.repetition_penalty,
+            top_k=req.top_k, min_p=req.min_p,
             stop=req.stop, model=req.model, stream=False)
         resp = completions(creq)
         if resp.status_code != 200:

@@ -14,6 +14,9 @@ examples/llama2-7b/server.yaml, container-contract.md:50-56) — loads
 - PARAM_W4_RESIDENT / W4_RESIDENT ("1" or "true", with MODEL_LOAD_IN_4BIT):
   drop the bf16 masters of the 4-bit weights; prefill runs the int4 GEMM
   and the freed memory becomes KV cache.
+- PARAM_BATCH_SAMPLER / BATCH_SAMPLER ("1" or "true"): sample each decode
+  batch with the batched per-request sampler (one launch, one download);
+  unset leaves the engine's RB_BATCH_SAMPLER default.
 - TP: tensor parallelism degree (defaults to visible GPU count); ranks
   are spawned via torch.distributed.run over RCCL/xGMI.
 """
@@ -111,12 +114,18 @@ def main():
     resident = os.environ.get(
         "PARAM_W4_RESIDENT",
         os.environ.get("W4_RESIDENT", "")).lower() in ("1", "true")
+    # PARAM_BATCH_SAMPLER / BATCH_SAMPLER: sample every decode batch with
+    # the one-launch per-request sampler (unset leaves RB_BATCH_SAMPLER)
+    bsampler = os.environ.get(
+        "PARAM_BATCH_SAMPLER",
+        os.environ.get("BATCH_SAMPLER", "")).lower() in ("1", "true")
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
                     kv_fp8=kv_fp8, w4_resident=resident or None,
                     # unset leaves the engine's own RB_* env defaults
                     prefill_from_cache=from_cache or None,
                     prefill_chunk=chunk or None,
-                    prefill_batch=pbatch or None)
+                    prefill_batch=pbatch or None,
+                    batch_sampler=bsampler or None)
     tok = load_tokenizer(model_dir if model_dir.exists() else None)
     if comm.rank() == 0:
         serve_forever(engine, tok, port=int(os.environ.get("PORT", "8080")),
