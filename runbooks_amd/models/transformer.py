@@ -81,7 +81,7 @@ class Attention(nn.Module):
         self.o_proj = RowParallelLinear(cfg.num_heads * self.dh, cfg.hidden_size,
                                         bias=cfg.attn_bias, tp_size=tp, dtype=dtype)
 
-    def _qkv(self, x, cos, sin, positions):
+    def _qkv(self, x, cos, sin, positions, lora=None):
         # x: [T, hidden] token-major
         T = x.shape[0]
         if getattr(self, "_qkv_w", None) is not None and \
@@ -91,6 +91,9 @@ class Attention(nn.Module):
             qo = self.hq * self.dh
             kvo = self.hkv * self.dh
             y = ops.fast_linear(x, self._qkv_w)
+            if lora is not None:
+                # per-row adapter deltas land before RoPE (serve/lora.py)
+                lora.patch_(y, x, "qkv")
             q = y[:, :qo].contiguous().view(T, self.hq, self.dh)
             k = y[:, qo:qo + kvo].contiguous().view(T, self.hkv, self.dh)
             v = y[:, qo + kvo:].contiguous().view(T, self.hkv, self.dh)
@@ -111,40 +114,55 @@ class Attention(nn.Module):
         o = ops.causal_attention(q, k, v, scale=self.scale)
         return self.o_proj(o.reshape(B * S, self.hq * self.dh))
 
-    def forward_prefill(self, x, cos, sin, positions, kc, vc, slot_mapping, B, S):
-        q, k, v = self._qkv(x, cos, sin, positions)
+    def _o_lora(self, o2, lora):
+        """o_proj for a batch with adapters: the base GEMM to a bf16
+        row-major y, then the rows' deltas on top."""
+        out = self.o_proj(o2)
+        return lora.patch_(out, o2, "o")
+
+    def forward_prefill(self, x, cos, sin, positions, kc, vc, slot_mapping, B, S,
+                        lora=None):
+        q, k, v = self._qkv(x, cos, sin, positions, lora)
         ops.kv_append(k, v, kc, vc, slot_mapping)
         q = q.view(B, S, self.hq, self.dh)
         o = ops.flash_prefill(q, k.view(B, S, self.hkv, self.dh),
                               v.view(B, S, self.hkv, self.dh), scale=self.scale)
+        if lora is not None:
+            return self._o_lora(o.reshape(B * S, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(B * S, self.hq * self.dh))
 
     def forward_prefill_paged(self, x, cos, sin, positions, kc, vc,
-                              slot_mapping, block_table, ctx_len):
+                              slot_mapping, block_table, ctx_len,
+                              lora=None):
         """One chunk of one sequence: append its k/v, then attend over the
         whole cached prefix + chunk through the block table."""
         T = x.shape[0]
-        q, k, v = self._qkv(x, cos, sin, positions)
+        q, k, v = self._qkv(x, cos, sin, positions, lora)
         ops.kv_append(k, v, kc, vc, slot_mapping)
         o = ops.paged_prefill(q, kc, vc, block_table, ctx_len,
                               scale=self.scale)
+        if lora is not None:
+            return self._o_lora(o.reshape(T, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(T, self.hq * self.dh))
 
     def forward_prefill_paged_batch(self, x, cos, sin, positions, kc, vc,
-                                    slot_mapping, block_tables, plan):
+                                    slot_mapping, block_tables, plan,
+                                    lora=None):
         """Several sequences' chunks packed in x [Ttot, hidden]: append all
         their k/v (per token), then attend each sequence through its own
         block-table row and context length (ops.paged_prefill_plan)."""
         T = x.shape[0]
-        q, k, v = self._qkv(x, cos, sin, positions)
+        q, k, v = self._qkv(x, cos, sin, positions, lora)
         ops.kv_append(k, v, kc, vc, slot_mapping)
         o = ops.paged_prefill_batch(q, kc, vc, block_tables, plan,
                                     scale=self.scale)
+        if lora is not None:
+            return self._o_lora(o.reshape(T, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(T, self.hq * self.dh))
 
     def forward_decode(self, x, cos, sin, positions, kc, vc, slot_mapping,
                        block_tables, seq_lens, nsplit=None, slab_ok=False,
-                       seq_starts=None):
+                       seq_starts=None, lora=None):
         B = x.shape[0]
         if getattr(self, "_qkv_w", None) is not None and \
                 self.cfg.pos == "rope" and ops.use_hip(x) and \
@@ -154,7 +172,14 @@ class Attention(nn.Module):
             # fp8 caches take the generic path below (rope + fp8-quant
             # kv_append): that mode targets long-context KV-bound decode
             # where the attention read, not the epilogue, dominates.
-            if ops.fused_epilogue_ok(x, self._qkv_w, "rope16"):
+            if lora is not None:
+                # the q/k deltas must land before RoPE: plain GEMM, the
+                # rows' deltas, then the standalone rope + append kernel
+                y = ops.fast_linear(x, self._qkv_w)
+                lora.patch_(y, x, "qkv")
+                q = ops.ext().qkv_rope_append(y, cos, sin, positions, kc,
+                                              vc, slot_mapping, self.hq)
+            elif ops.fused_epilogue_ok(x, self._qkv_w, "rope16"):
                 # rope16 weight layout: the GEMM epilogue does the rope +
                 # append itself (csrc/decode_gemm.hip), no second kernel
                 q = ops.decode_linear_rope_append(
@@ -165,7 +190,7 @@ class Attention(nn.Module):
                 q = ops.ext().qkv_rope_append(y, cos, sin, positions, kc,
                                               vc, slot_mapping, self.hq)
         else:
-            q, k, v = self._qkv(x, cos, sin, positions)
+            q, k, v = self._qkv(x, cos, sin, positions, lora)
             ops.kv_append(k, v, kc, vc, slot_mapping)
         o, oswz = ops.paged_decode_with_operand(
             q, kc, vc, block_tables, seq_lens, scale=self.scale,
@@ -173,6 +198,9 @@ class Attention(nn.Module):
         o2 = o.reshape(B, self.hq * self.dh)
         if oswz is not None:
             o2._rb_swz = oswz
+        if lora is not None:
+            # bf16 output (no split-K slab): the delta is added to it
+            return self._o_lora(o2, lora)
         if slab_ok and self.tp == 1 and self.o_proj.bias is None:
             out, _ = ops.decode_linear_raw(o2, self.o_proj.weight)
             return out
@@ -209,7 +237,35 @@ class MLP(nn.Module):
                                        xs=swz, m=m)
         return out
 
-    def forward(self, x, slab_ok=False):
+    def _forward_lora(self, x, lora):
+        """Batch with adapters (fused gate-up models): every GEMM is the
+        plain base GEMM to a bf16 row-major output that the rows' deltas
+        are added to, so no fused GLU epilogue and no split-K slab."""
+        gelu = self.act == "gelu_glu"
+        y = ops.fast_linear(x, self._gateup_w)
+        lora.patch_(y, x, "gateup")
+        half = y.shape[-1] // 2
+        if ops.use_hip(y):
+            ext = ops.ext()
+            if (y.dtype == torch.bfloat16 and half % 16 == 0 and
+                    y.numel() // y.shape[-1] <= 32):
+                h, swz = (ext.geglu_packed_dec(y) if gelu
+                          else ext.swiglu_packed_dec(y))
+                h._rb_swz = swz
+            else:
+                h = ext.geglu_packed(y) if gelu else ext.swiglu_packed(y)
+        elif gelu:
+            h = torch.nn.functional.gelu(y[:, :half],
+                                         approximate="tanh") * y[:, half:]
+        else:
+            h = ops.swiglu(y[:, :half].contiguous(),
+                           y[:, half:].contiguous())
+        out = self.down_proj(h)
+        return lora.patch_(out, h, "down")
+
+    def forward(self, x, slab_ok=False, lora=None):
+        if lora is not None:
+            return self._forward_lora(x, lora)
         if self.act == "silu_glu":
             if getattr(self, "_gateup_w", None) is not None and \
                     not torch.is_grad_enabled():
@@ -283,7 +339,7 @@ class Block(nn.Module):
         self.norm1 = _norm_module(cfg, dtype)
         self.norm2 = None if cfg.single_norm else _norm_module(cfg, dtype)
 
-    def forward(self, x, attn_fn):
+    def forward(self, x, attn_fn, lora=None):
         """attn_fn(h) runs the right attention mode on normed input."""
         if self.cfg.parallel_residual:
             if self.cfg.single_norm:
@@ -292,10 +348,11 @@ class Block(nn.Module):
                 return x + attn_fn(h) + self.mlp(h)
             # falcon-40b: x + attn(ln_attn(x)) + mlp(ln_mlp(x))
             return x + attn_fn(self.norm1(x)) + self.mlp(self.norm2(x))
+        # (adapters, ``lora``, are served on this sequential form only)
         x = x + attn_fn(self.norm1(x))
-        return x + self.mlp(self.norm2(x))
+        return x + self.mlp(self.norm2(x), lora=lora)
 
-    def forward_decode_fused(self, x_base, delta, attn_fn):
+    def forward_decode_fused(self, x_base, delta, attn_fn, lora=None):
         """Decode hot path (sequential-residual RMSNorm models): the
         residual add is fused into the next norm's kernel
         (rmsnorm_res_fwd_dec), so the layer's residual chain costs zero
@@ -319,6 +376,8 @@ class Block(nn.Module):
         a = attn_fn(y1)
         xr2, y2, s2 = res_norm(xr1, a, self.norm2.weight, self.norm2.eps)
         y2._rb_swz = s2
+        if lora is not None:
+            return xr2, self.mlp(y2, lora=lora)
         return xr2, self.mlp(y2, slab_ok=True)
 
 
@@ -412,23 +471,35 @@ class Transformer(nn.Module):
         self.grad_checkpointing = enabled
 
     # -- serving ---------------------------------------------------------------
+    def _lora_layers(self, lora, bounds=None):
+        """Per-block ``lora`` views (serve/lora.py LoraBatch), or None
+        per block without adapters. ``bounds``: the sequences' row
+        boundaries of a prefill; None for decode (one row per slot)."""
+        if lora is None:
+            return [None] * len(self.blocks)
+        spans = None if bounds is None else lora.seq_spans(bounds)
+        return [lora.at(i, spans) for i in range(len(self.blocks))]
+
     @torch.no_grad()
-    def prefill(self, tokens, positions, caches, slot_mapping):
+    def prefill(self, tokens, positions, caches, slot_mapping, lora=None):
         """tokens [B, S]; caches: list of (k_cache, v_cache) per layer.
-        Returns last-position logits [B, V]."""
+        Returns last-position logits [B, V]. ``lora`` (here and below): a
+        serve.lora.LoraBatch naming each sequence's adapter slot."""
         B, S = tokens.shape
         x = self._embed(tokens, positions)
-        for blk, (kc, vc) in zip(self.blocks, caches):
-            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_prefill(  # noqa: E731
-                h, self.rope_cos, self.rope_sin, positions, kc, vc, slot_mapping, B, S)
-            x = blk(x, fn)
+        lls = self._lora_layers(lora, [b * S for b in range(B + 1)])
+        for blk, (kc, vc), ll in zip(self.blocks, caches, lls):
+            fn = lambda h, b=blk, kc=kc, vc=vc, ll=ll: b.attn.forward_prefill(  # noqa: E731
+                h, self.rope_cos, self.rope_sin, positions, kc, vc,
+                slot_mapping, B, S, lora=ll)
+            x = blk(x, fn, lora=ll)
         x = self.norm_f(x.view(B, S, -1)[:, -1])
         logits = self.lm_head(x)
         return gather_from_tp(logits) if self._lm_vocab_parallel else logits
 
     @torch.no_grad()
     def prefill_paged(self, tokens, positions, caches, slot_mapping,
-                      block_table, ctx_len):
+                      block_table, ctx_len, lora=None):
         """Prefill tokens [1, T] of ONE sequence whose first ``ctx_len``
         positions are already in the paged cache (prefix-cache hit or an
         earlier chunk). ``positions`` are absolute ([T], starting at
@@ -437,18 +508,19 @@ class Transformer(nn.Module):
         assert tokens.shape[0] == 1, "prefill_paged takes one sequence"
         T = tokens.shape[1]
         x = self._embed(tokens, positions)
-        for blk, (kc, vc) in zip(self.blocks, caches):
-            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_prefill_paged(  # noqa: E731
+        lls = self._lora_layers(lora, [0, T])
+        for blk, (kc, vc), ll in zip(self.blocks, caches, lls):
+            fn = lambda h, b=blk, kc=kc, vc=vc, ll=ll: b.attn.forward_prefill_paged(  # noqa: E731
                 h, self.rope_cos, self.rope_sin, positions, kc, vc,
-                slot_mapping, block_table, ctx_len)
-            x = blk(x, fn)
+                slot_mapping, block_table, ctx_len, lora=ll)
+            x = blk(x, fn, lora=ll)
         x = self.norm_f(x.view(1, T, -1)[:, -1])
         logits = self.lm_head(x)
         return gather_from_tp(logits) if self._lm_vocab_parallel else logits
 
     @torch.no_grad()
     def prefill_paged_batch(self, tokens, positions, caches, slot_mapping,
-                            block_tables, plan):
+                            block_tables, plan, lora=None):
         """Prefill the chunks of B sequences in one pass. tokens [Ttot],
         absolute positions [Ttot] and slot_mapping [Ttot] are the chunks
         packed back to back as ``plan`` (ops.paged_prefill_plan) lays them
@@ -459,11 +531,12 @@ class Transformer(nn.Module):
         assert tokens.dim() == 1 and tokens.shape[0] == plan.total, \
             "prefill_paged_batch takes the plan's packed tokens"
         x = self._embed(tokens, positions)
-        for blk, (kc, vc) in zip(self.blocks, caches):
-            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_prefill_paged_batch(  # noqa: E731
+        lls = self._lora_layers(lora, plan.cu_q)
+        for blk, (kc, vc), ll in zip(self.blocks, caches, lls):
+            fn = lambda h, b=blk, kc=kc, vc=vc, ll=ll: b.attn.forward_prefill_paged_batch(  # noqa: E731
                 h, self.rope_cos, self.rope_sin, positions, kc, vc,
-                slot_mapping, block_tables, plan)
-            x = blk(x, fn)
+                slot_mapping, block_tables, plan, lora=ll)
+            x = blk(x, fn, lora=ll)
         # only each sequence's last row reaches the vocabulary GEMM
         x = self.norm_f(x.index_select(0, plan.last_rows()))
         logits = self.lm_head(x)
@@ -471,12 +544,16 @@ class Transformer(nn.Module):
 
     @torch.no_grad()
     def decode(self, tokens, positions, caches, slot_mapping, block_tables,
-               seq_lens, nsplit=None, seq_starts=None):
+               seq_lens, nsplit=None, seq_starts=None, lora=None):
         """tokens [B] (one new token per sequence) -> logits [B, V].
         ``nsplit`` fixes the paged-decode work split (required under
-        hipGraph capture, serve/graph.py)."""
+        hipGraph capture, serve/graph.py). ``lora``: a LoraBatch with one
+        adapter slot per row; each GEMM site then runs the plain base
+        GEMM plus ops.lora_shrink / ops.lora_expand_ instead of its fused
+        epilogue."""
         B = tokens.shape[0]
         x = self._embed(tokens.view(B, 1), positions)
+        lls = self._lora_layers(lora)
         import os as _os
         if (ops.use_hip(x) and x.dtype == torch.bfloat16 and B <= 32 and
                 self.cfg.norm == "rmsnorm" and
@@ -485,12 +562,12 @@ class Transformer(nn.Module):
                 _os.environ.get("RB_FUSED_RESID", "1") == "1"):
             # fused residual chain: zero standalone adds in the hot loop
             delta = None
-            for blk, (kc, vc) in zip(self.blocks, caches):
-                fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_decode(  # noqa: E731
+            for blk, (kc, vc), ll in zip(self.blocks, caches, lls):
+                fn = lambda h, b=blk, kc=kc, vc=vc, ll=ll: b.attn.forward_decode(  # noqa: E731
                     h, self.rope_cos, self.rope_sin, positions, kc, vc,
                     slot_mapping, block_tables, seq_lens, nsplit=nsplit,
-                    slab_ok=True, seq_starts=seq_starts)
-                x, delta = blk.forward_decode_fused(x, delta, fn)
+                    slab_ok=True, seq_starts=seq_starts, lora=ll)
+                x, delta = blk.forward_decode_fused(x, delta, fn, lora=ll)
             if delta.dtype == torch.float32:
                 _, y, swz = ops.ext().rmsnorm_res_slab_fwd_dec(
                     x, delta, self.norm_f.weight, self.norm_f.eps)
@@ -501,11 +578,12 @@ class Transformer(nn.Module):
             logits = self.lm_head(y)
             return (gather_from_tp(logits) if self._lm_vocab_parallel
                     else logits)
-        for blk, (kc, vc) in zip(self.blocks, caches):
-            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_decode(  # noqa: E731
+        for blk, (kc, vc), ll in zip(self.blocks, caches, lls):
+            fn = lambda h, b=blk, kc=kc, vc=vc, ll=ll: b.attn.forward_decode(  # noqa: E731
                 h, self.rope_cos, self.rope_sin, positions, kc, vc, slot_mapping,
-                block_tables, seq_lens, nsplit=nsplit, seq_starts=seq_starts)
-            x = blk(x, fn)
+                block_tables, seq_lens, nsplit=nsplit, seq_starts=seq_starts,
+                lora=ll)
+            x = blk(x, fn, lora=ll)
         x = self.norm_f(x)
         logits = self.lm_head(x)
         return gather_from_tp(logits) if self._lm_vocab_parallel else logits

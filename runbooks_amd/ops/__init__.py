@@ -16,6 +16,8 @@ from .kvcache import BLOCK_SIZE, alloc_kv_cache, kv_append, kv_append_ref  # noq
 from .linear import (Linear, decode_layout, decode_linear_glu,  # noqa: F401
                      decode_linear_raw, decode_linear_rope_append,
                      fast_linear, fused_epilogue_ok, w4_prefill_enabled)
+from .lora_serve import (lora_expand_, lora_expand_ref_, lora_shrink,  # noqa: F401
+                         lora_shrink_ref)
 from .norm import RMSNorm, rmsnorm, rmsnorm_ref  # noqa: F401
 from .rope import rope, rope_ref, rope_tables  # noqa: F401
 from .sampling import (SampleBatchResult, pack_sample_batch,  # noqa: F401

@@ -19,6 +19,9 @@ at::Tensor decode_swizzle_w_layout(at::Tensor w, int64_t layout, int64_t hq, int
                                    int64_t dh);
 at::Tensor lora_delta_(at::Tensor y, at::Tensor t, at::Tensor w, double scale, bool w_transposed);
 at::Tensor lora_badd_(at::Tensor y, at::Tensor t, at::Tensor w, double scale);
+at::Tensor lora_shrink(at::Tensor x, at::Tensor a_stack, at::Tensor idx, int64_t S);
+at::Tensor lora_expand_(at::Tensor y, at::Tensor t, at::Tensor b_stack, at::Tensor scales,
+                        at::Tensor idx, std::vector<int64_t> seg_ends);
 std::vector<at::Tensor> swiglu_packed_dec(at::Tensor y);
 std::vector<at::Tensor> geglu_packed_dec(at::Tensor y);
 std::vector<at::Tensor> rmsnorm_bwd(at::Tensor x, at::Tensor w, at::Tensor dy,
@@ -125,6 +128,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "in-place y += scale * t[T,r<=32] @ W[N,r]^T (LoRA merge)");
   m.def("lora_badd_", &lora_badd_,
         "MFMA in-place y += scale * t[T,16] @ W[N,16]^T (LoRA B merge)");
+  m.def("lora_shrink", &lora_shrink,
+        "per-row LoRA A product: t[M,S*R] = x[M,K] @ a_stack[idx[m]]^T (fp32 out)",
+        py::arg("x"), py::arg("a_stack"), py::arg("idx"), py::arg("S"));
+  m.def("lora_expand_", &lora_expand_,
+        "per-row LoRA B merge, in place: y[m] += scales[idx[m]] * t[m] @ "
+        "b_stack[idx[m]]^T per segment",
+        py::arg("y"), py::arg("t"), py::arg("b_stack"), py::arg("scales"),
+        py::arg("idx"), py::arg("seg_ends"));
   m.def("swiglu_packed_dec", &swiglu_packed_dec,
         "packed SwiGLU + decode-GEMM operand swizzle in one pass");
   m.def("geglu_packed_dec", &geglu_packed_dec,

@@ -107,6 +107,8 @@ class Request:
     computed: int = 0
     finished: bool = False
     created: float = field(default_factory=time.time)
+    # name of the LoRA adapter this request is served with (None = base)
+    adapter: str | None = None
 
     @property
     def seq_len(self) -> int:
@@ -123,7 +125,9 @@ class Engine:
                  prefill_chunk: int | None = None,
                  prefill_batch: int | None = None,
                  w4_resident: bool | None = None,
-                 batch_sampler: bool | None = None):
+                 batch_sampler: bool | None = None,
+                 max_loras: int | None = None,
+                 lora_rank: int | None = None):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
@@ -170,6 +174,33 @@ class Engine:
             print("engine: MODEL_LOAD_IN_8BIT ignored at TP>1 "
                   "(fp8 decode path is single-GPU; 288 GB/GPU rarely "
                   "needs 8-bit at TP>1)", flush=True)
+        # LoRA adapter serving (off by default): RB_MAX_LORAS=N /
+        # max_loras=N > 0 preallocates N adapter slots of rank
+        # RB_LORA_RANK / lora_rank (serve/lora.py) before the KV pool is
+        # sized; requests then pick an adapter by name and a decode batch
+        # may mix them. With 0 nothing is allocated and every path below
+        # is the adapter-free one.
+        self.max_loras = int(max_loras if max_loras is not None
+                             else _os1.environ.get("RB_MAX_LORAS", "0") or 0)
+        self.lora_rank = int(lora_rank if lora_rank is not None
+                             else _os1.environ.get("RB_LORA_RANK", "16")
+                             or 16)
+        self.lora_pool = None
+        if self.max_loras < 0:
+            raise ValueError(f"max_loras must be >= 0, got {self.max_loras}")
+        if self.max_loras > 0:
+            if comm.world_size() > 1 or model.tp > 1:
+                raise NotImplementedError(
+                    "max_loras > 0: adapter serving is single-GPU (TP=1)")
+            from .lora import AdapterPool
+            if not torch.cuda.is_available():
+                # the CPU reference path serves adapters through the same
+                # fused qkv / gate-up sites
+                from ..models.transformer import fuse_for_inference
+                if getattr(self.model.blocks[0].attn, "_qkv_w", None) is None:
+                    fuse_for_inference(self.model)
+            self.lora_pool = AdapterPool(self.model, self.max_loras,
+                                         self.lora_rank)
         self.cfg = model.cfg
         if torch.cuda.is_available() and model.cfg.head_dim not in (64, 128,
                                                                     256):
@@ -190,6 +221,11 @@ class Engine:
         import os as _os0
         self.kv_fp8 = (kv_fp8 if kv_fp8 is not None
                        else _os0.environ.get("RB_KV_FP8", "0") == "1")
+        if self.kv_fp8 and self.lora_pool is not None:
+            raise NotImplementedError(
+                "max_loras > 0 with an fp8 KV cache (RB_KV_FP8) is not "
+                "supported: adapter batches are validated on the bf16 "
+                "cache only; serve adapters with kv_fp8 off")
         if kv_blocks is None:
             kv_blocks = self._auto_kv_blocks(mem_fraction)
         if comm.is_dist() and comm.world_size() > 1 and model.tp > 1:
@@ -306,6 +342,9 @@ class Engine:
                       "prefill_chunks": 0, "prefill_batches": 0,
                       "prefill_batched_requests": 0,
                       "sampler_batched_steps": 0}
+        if self.lora_pool is not None:
+            self.stats["lora_decode_steps"] = 0
+            self.stats["lora_rows"] = 0
 
     def _auto_kv_blocks(self, mem_fraction: float) -> int:
         elem = (self.cfg.head_dim + 16) if self.kv_fp8 \
@@ -327,15 +366,81 @@ class Engine:
                frequency_penalty: float = 0.0,
                repetition_penalty: float = 1.0,
                stop_token_ids: tuple[int, ...] = (),
-               top_k: int = 0, min_p: float = 0.0) -> Request:
+               top_k: int = 0, min_p: float = 0.0,
+               adapter: str | None = None) -> Request:
+        if adapter is not None and (self.lora_pool is None
+                                    or adapter not in self.lora_pool):
+            raise KeyError(f"no adapter named {adapter!r} is loaded")
         req = Request(self._next_id, list(prompt_ids), max_new_tokens,
                       temperature, top_p, logprobs, seed,
                       presence_penalty, frequency_penalty,
                       repetition_penalty, tuple(stop_token_ids),
                       int(top_k or 0), float(min_p or 0.0))
+        req.adapter = adapter
         self._next_id += 1
         self.waiting.append(req)
         return req
+
+    # -- adapters ---------------------------------------------------------------
+    def _need_pool(self):
+        if self.lora_pool is None:
+            raise RuntimeError("this engine serves no adapters: construct it "
+                               "with max_loras > 0 (RB_MAX_LORAS)")
+        return self.lora_pool
+
+    def load_adapter(self, name: str, path) -> None:
+        """Read a LoRA adapter (trainer checkpoint or HF PEFT directory)
+        into a free slot. Copies on the current stream between steps:
+        call it from the thread that steps the engine (EngineLoop queues
+        it)."""
+        self._need_pool().load(name, path)
+
+    def load_adapter_state(self, name: str, state: dict, alpha: float,
+                           r: int | None = None) -> None:
+        """load_adapter for tensors already in memory (serve/lora.py
+        read_adapter); the same threading rule holds."""
+        self._need_pool().load_state(name, state, alpha, r)
+
+    def unload_adapter(self, name: str) -> None:
+        pool = self._need_pool()
+        pool.slot_of(name)          # KeyError for an unknown name
+        live = list(self.waiting) + list(self.running)
+        if self.prefilling is not None:
+            live.append(self.prefilling)
+        users = [r.request_id for r in live if r.adapter == name]
+        if users:
+            raise RuntimeError(f"adapter {name!r} is in use by request(s) "
+                               f"{users}; unload it once they finish")
+        if self.prefix_cache_enabled:
+            # a later adapter of the same name must not hit on this one's
+            # K/V
+            for key in [k for k in self._pc
+                        if k and isinstance(k[0], str) and k[0] == name]:
+                self.allocator.release([self._pc.pop(key)])
+        pool.unload(name)
+
+    def adapters(self) -> list[str]:
+        return [] if self.lora_pool is None else self.lora_pool.loaded()
+
+    def _lora_for(self, reqs: list[Request]):
+        """LoraBatch for these rows / sequences, None when none of them
+        has an adapter (the adapter-free call is then made unchanged)."""
+        if self.lora_pool is None or all(r.adapter is None for r in reqs):
+            return None
+        from .lora import LoraBatch
+        return LoraBatch(self.lora_pool, self._lora_slots(reqs))
+
+    def _lora_slots(self, reqs: list[Request]) -> list[int]:
+        pool = self.lora_pool
+        return [-1 if r.adapter is None else pool.slot_of(r.adapter)
+                for r in reqs]
+
+    def _pc_key(self, req: Request, n_tokens: int) -> tuple:
+        """Prefix-cache key of the request's first n_tokens prompt tokens.
+        K/V depend on the adapter, so its name leads the key: two adapters
+        never share a block, requests of one adapter still do."""
+        key = tuple(req.prompt_ids[:n_tokens])
+        return key if req.adapter is None else (req.adapter,) + key
 
     @staticmethod
     def _apply_penalties(row, r: Request):
@@ -383,7 +488,7 @@ class Engine:
         hits: list[tuple[tuple, int]] = []
         if self.prefix_cache_enabled:
             for k in range(1, S // self.bs + 1):
-                key = tuple(req.prompt_ids[:k * self.bs])
+                key = self._pc_key(req, k * self.bs)
                 b = self._pc.get(key)
                 if b is None:
                     break
@@ -429,7 +534,7 @@ class Engine:
         chunks (cache holds its own reference per block)."""
         S = len(req.prompt_ids)
         for k in range(1, S // self.bs + 1):
-            key = tuple(req.prompt_ids[:k * self.bs])
+            key = self._pc_key(req, k * self.bs)
             if key not in self._pc:
                 b = req.blocks[k - 1]
                 self._pc[key] = b
@@ -458,7 +563,13 @@ class Engine:
         if self.tp > 1:
             from .tp_worker import broadcast_prefill
             broadcast_prefill(tokens, positions, slots)
-        logits = self.model.prefill(tokens, positions, self.caches, slots)
+        lora = self._lora_for([req])
+        if lora is None:
+            logits = self.model.prefill(tokens, positions, self.caches,
+                                        slots)
+        else:
+            logits = self.model.prefill(tokens, positions, self.caches,
+                                        slots, lora=lora)
         return self._sample_first(req, logits)
 
     def _sample_first(self, req: Request, logits) -> int:
@@ -501,8 +612,13 @@ class Engine:
         nb = (end + self.bs - 1) // self.bs
         bt = torch.tensor(req.blocks[:nb], dtype=torch.int32,
                           device=self.device)
-        logits = self.model.prefill_paged(tokens, positions, self.caches,
-                                          slots, bt, start)
+        lora = self._lora_for([req])
+        if lora is None:
+            logits = self.model.prefill_paged(tokens, positions, self.caches,
+                                              slots, bt, start)
+        else:
+            logits = self.model.prefill_paged(tokens, positions, self.caches,
+                                              slots, bt, start, lora=lora)
         self.stats["prefill_tokens"] += end - start
         if getattr(req, "_chunked", False):
             self.stats["prefill_chunks"] += 1
@@ -559,11 +675,11 @@ class Engine:
             hits = 0
             if self.prefix_cache_enabled:
                 while (hits + 1) * self.bs <= S and \
-                        tuple(cand.prompt_ids[:(hits + 1) * self.bs]) \
+                        self._pc_key(cand, (hits + 1) * self.bs) \
                         in self._pc:
                     hits += 1
                 if (hits + 1) * self.bs <= S and \
-                        tuple(cand.prompt_ids[:(hits + 1) * self.bs]) \
+                        self._pc_key(cand, (hits + 1) * self.bs) \
                         in publish:
                     break
             rem = S - (min(hits * self.bs, S - 1)
@@ -582,7 +698,7 @@ class Engine:
             total += rem
             if self.prefix_cache_enabled:
                 for k in range(hits + 1, S // self.bs + 1):
-                    publish.add(tuple(req.prompt_ids[:k * self.bs]))
+                    publish.add(self._pc_key(req, k * self.bs))
         return batch
 
     def _prefill_batch(self, reqs: list[Request]) -> list[int]:
@@ -616,11 +732,12 @@ class Engine:
         for i, r in enumerate(reqs):
             nb = (len(r.prompt_ids) + self.bs - 1) // self.bs
             bt[i, :nb] = torch.tensor(r.blocks[:nb], dtype=torch.int32)
+        lora = self._lora_for(reqs)
         logits = self.model.prefill_paged_batch(
             torch.tensor(toks, dtype=torch.long, device=dev),
             torch.tensor(pos, dtype=torch.int32, device=dev), self.caches,
             torch.tensor(slots, dtype=torch.int32, device=dev),
-            bt.to(dev), plan)
+            bt.to(dev), plan, **({} if lora is None else {"lora": lora}))
         first = [self._sample_first(r, logits[i:i + 1])
                  for i, r in enumerate(reqs)]
         for r, t, c in zip(reqs, q_lens, ctx_lens):
@@ -653,6 +770,11 @@ class Engine:
         W = self.cfg.sliding_window
         starts = [max(0, v + 1 - W) if W else 0 for v in vpos]
 
+        if self.lora_pool is not None and \
+                any(r.adapter is not None for r in reqs):
+            return self._sample_batch(
+                self._decode_lora(reqs, last, pos, slots, vpos, starts),
+                reqs)
         if self.use_graphs and B <= self.max_batch:
             if self._graphed is None:
                 from .graph import GraphedDecoder
@@ -682,6 +804,41 @@ class Engine:
             logits = self.model.decode(tokens, positions, self.caches, slot_t,
                                        bt, seq_lens, seq_starts=start_t)
         return self._sample_batch(logits, reqs)
+
+    def _decode_lora(self, reqs, last, pos, slots, vpos, starts):
+        """The decode step of a batch in which at least one row has an
+        adapter: the same call with ``lora=``, through the graph family
+        keyed (bucket, "lora") under graphs."""
+        B = len(reqs)
+        dev = self.device
+        lslots = self._lora_slots(reqs)
+        self.stats["lora_decode_steps"] += 1
+        self.stats["lora_rows"] += sum(1 for s in lslots if s >= 0)
+        if self.use_graphs and B <= self.max_batch:
+            if self._graphed is None:
+                from .graph import GraphedDecoder
+                self._graphed = GraphedDecoder(
+                    self.model, self.caches, self.max_batch,
+                    self.max_blocks_per_seq, self.dummy_block, dev)
+            if self._graphed.lora_pool is None:
+                self._graphed.enable_lora(self.lora_pool)
+            return self._graphed.decode(last, pos, slots,
+                                        [r.blocks for r in reqs],
+                                        [v + 1 for v in vpos], starts,
+                                        adapter_slots=lslots)
+        from .lora import LoraBatch
+        maxb = max(len(r.blocks) for r in reqs)
+        bt = torch.zeros(B, maxb, dtype=torch.int32)
+        for i, r in enumerate(reqs):
+            bt[i, :len(r.blocks)] = torch.tensor(r.blocks, dtype=torch.int32)
+        return self.model.decode(
+            torch.tensor(last, dtype=torch.long, device=dev),
+            torch.tensor(pos, dtype=torch.int32, device=dev), self.caches,
+            torch.tensor(slots, dtype=torch.int32, device=dev), bt.to(dev),
+            torch.tensor([v + 1 for v in vpos], dtype=torch.int32,
+                         device=dev),
+            seq_starts=torch.tensor(starts, dtype=torch.int32, device=dev),
+            lora=LoraBatch(self.lora_pool, lslots))
 
     def _use_batch_sampler(self, reqs: list[Request]) -> bool:
         return self.batch_sampler or any(r.top_k > 0 or r.min_p > 0.0
@@ -878,7 +1035,7 @@ class Engine:
             need = (len(head.prompt_ids) + self.bs - 1) // self.bs + 1
             if self.prefix_cache_enabled:
                 for k in range(1, len(head.prompt_ids) // self.bs + 1):
-                    if tuple(head.prompt_ids[:k * self.bs]) in self._pc:
+                    if self._pc_key(head, k * self.bs) in self._pc:
                         need -= 1
                     else:
                         break

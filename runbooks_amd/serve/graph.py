@@ -68,9 +68,25 @@ class GraphedDecoder:
         self._np = self.h_staging.numpy()
         self.graphs = {}     # bucket -> (CUDAGraph, logits_out)
         self._pool = None
+        self.lora_pool = None   # serve/lora.py AdapterPool (enable_lora)
+
+    def enable_lora(self, pool) -> None:
+        """Second graph family, keyed (bucket, "lora"), for batches in
+        which a row has an adapter: the same decode captured with
+        ``lora=`` over one more static buffer, ``adapter_idx`` (-1 = no
+        adapter, padding rows included), filled from its own pinned
+        staging tensor. The adapter-free family and ``h_staging`` are
+        untouched."""
+        B = self.tokens.shape[0]
+        self.lora_pool = pool
+        self.adapter_idx = torch.full((B,), -1, dtype=torch.int32,
+                                      device=self.device)
+        self.h_adapter = torch.full((B,), -1, dtype=torch.int32,
+                                    pin_memory=torch.cuda.is_available())
+        self._np_adapter = self.h_adapter.numpy()
 
     # -- capture -----------------------------------------------------------
-    def _capture(self, b: int):
+    def _capture(self, b: int, lora: bool = False):
         hkv = self.model.local_kv_heads()
         from ..ops.attention import _is_vt
         nsplit = fixed_nsplit(b, hkv,
@@ -78,6 +94,9 @@ class GraphedDecoder:
         args = (self.tokens[:b], self.positions[:b], self.caches,
                 self.slots[:b], self.block_tables[:b], self.seq_lens[:b])
         kw = dict(nsplit=nsplit, seq_starts=self.seq_starts[:b])
+        if lora:
+            from .lora import LoraBatch
+            kw["lora"] = LoraBatch(self.lora_pool, idx=self.adapter_idx[:b])
         # warmup outside the graph (allocator + autotune settle)
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
@@ -94,18 +113,23 @@ class GraphedDecoder:
         else:
             with torch.cuda.graph(g, pool=self._pool):
                 out = self.model.decode(*args, **kw)
-        self.graphs[b] = (g, out)
+        self.graphs[(b, "lora") if lora else b] = (g, out)
 
     # -- replay ------------------------------------------------------------
     def decode(self, tokens, positions, slots, block_rows, seq_lens,
-               seq_starts=None):
+               seq_starts=None, adapter_slots=None):
         """All args host lists; block_rows is a list of per-seq block lists.
-        Returns logits [len(tokens), V] (a view into the static output)."""
+        Returns logits [len(tokens), V] (a view into the static output).
+        ``adapter_slots`` (one adapter slot per row, -1 = none; needs
+        enable_lora) replays the "lora" graph family."""
         n = len(tokens)
         b = next(x for x in self.buckets if x >= n)
-        if b not in self.graphs:
-            self._capture(b)
-        g, out = self.graphs[b]
+        key = b if adapter_slots is None else (b, "lora")
+        if adapter_slots is not None:
+            self._stage_adapters(b, adapter_slots)
+        if key not in self.graphs:
+            self._capture(b, lora=adapter_slots is not None)
+        g, out = self.graphs[key]
         bt = self._stage(b, tokens, positions, slots, block_rows, seq_lens,
                          seq_starts or [0] * n)
 
@@ -116,8 +140,24 @@ class GraphedDecoder:
         self.seq_lens[:b].copy_(h[3 * b:4 * b], non_blocking=True)
         self.seq_starts[:b].copy_(h[4 * b:5 * b], non_blocking=True)
         self.block_tables[:b].copy_(bt, non_blocking=True)
+        if adapter_slots is not None:
+            self.adapter_idx[:b].copy_(self.h_adapter[:b], non_blocking=True)
         g.replay()
         return out[:n]
+
+    def _stage_adapters(self, b, adapter_slots) -> None:
+        """Range-check the rows' adapter slots on the host (the kernels
+        only index with them) and stage them; padding rows get -1."""
+        if self.lora_pool is None:
+            raise RuntimeError("adapter_slots given before enable_lora()")
+        n = len(adapter_slots)
+        top = self.lora_pool.max_loras
+        for i, s in enumerate(adapter_slots):
+            if not -1 <= s < top:
+                raise ValueError(f"adapter slot {s} of row {i} is out of "
+                                 f"range (-1..{top - 1})")
+        self._np_adapter[:n] = adapter_slots
+        self._np_adapter[n:b] = -1
 
     def _stage(self, b, tokens, positions, slots, block_rows, seq_lens,
                seq_starts):

@@ -107,6 +107,9 @@ class EngineLoop:
         self._watchers: dict[int, queue.Queue] = {}  # request_id -> token q
         self._failures = 0
         self._stop = False
+        # calls that must run on the stepping thread, between steps
+        # (adapter load / unload copy into memory the decode step reads)
+        self._jobs: queue.Queue = queue.Queue()
         self._thread = threading.Thread(target=self._run, daemon=True)
         self._thread.start()
 
@@ -115,7 +118,7 @@ class EngineLoop:
                presence_penalty=0.0, frequency_penalty=0.0,
                repetition_penalty=1.0,
                stop_token_ids=(), top_k=0,
-               min_p=0.0) -> tuple[queue.Queue, "object"]:
+               min_p=0.0, adapter=None) -> tuple[queue.Queue, "object"]:
         """Returns (queue yielding token_id | None, engine Request)."""
         q: queue.Queue = queue.Queue()
         with self._lock:
@@ -126,7 +129,9 @@ class EngineLoop:
                                      frequency_penalty=frequency_penalty,
                                      repetition_penalty=repetition_penalty,
                                      stop_token_ids=stop_token_ids,
-                                     top_k=top_k, min_p=min_p)
+                                     top_k=top_k, min_p=min_p,
+                                     **({} if adapter is None
+                                        else {"adapter": adapter}))
             self._watchers[req.request_id] = q
             req._watch_sent = 0
         self._wake.set()
@@ -136,8 +141,47 @@ class EngineLoop:
         with self._lock:
             self.engine.cancel(request_id)
 
+    def call(self, fn, timeout: float | None = 60.0):
+        """Run fn() on the stepping thread between two steps and return
+        its result (or raise what it raised)."""
+        box: dict = {}
+        done = threading.Event()
+        self._jobs.put((fn, box, done))
+        self._wake.set()
+        if not done.wait(timeout):
+            raise TimeoutError("engine loop did not run the call")
+        if "error" in box:
+            raise box["error"]
+        return box.get("result")
+
+    def load_adapter(self, name: str, path) -> None:
+        """The file is read here, on the caller's thread and outside the
+        lock, so submits and cancels are not held up by it; only the copy
+        into the slot runs on the stepping thread."""
+        from .lora import read_adapter
+        state, alpha, r = read_adapter(path, self.engine.cfg)
+        self.call(lambda: self.engine.load_adapter_state(name, state, alpha,
+                                                         r))
+
+    def unload_adapter(self, name: str) -> None:
+        self.call(lambda: self.engine.unload_adapter(name))
+
+    def _run_jobs(self) -> None:
+        while True:
+            try:
+                fn, box, done = self._jobs.get_nowait()
+            except queue.Empty:
+                return
+            with self._lock:
+                try:
+                    box["result"] = fn()
+                except Exception as e:  # noqa: BLE001
+                    box["error"] = e
+            done.set()
+
     def _run(self):
         while not self._stop:
+            self._run_jobs()
             if not self.engine.has_work():
                 self._wake.wait(timeout=0.05)
                 self._wake.clear()
@@ -244,19 +288,38 @@ def build_app(engine: Engine, tokenizer=None,
     def healthz():
         return {"status": "ok"}
 
+    def _not_found(model_id: str):
+        return JSONResponse(status_code=404, content={"error": {
+            "message": f"model '{model_id}' not found"}})
+
+    def _adapter_card(name: str):
+        return {"id": name, "object": "model", "owned_by": "runbooks-amd",
+                "parent": model_name}
+
     @app.get("/v1/models")
     def models():
         return {"object": "list",
                 "data": [{"id": model_name, "object": "model",
-                          "owned_by": "runbooks-amd"}]}
+                          "owned_by": "runbooks-amd"}] +
+                        [_adapter_card(a) for a in engine.adapters()]}
 
     @app.get("/v1/models/{model_id}")
     def model_info(model_id: str):
+        if model_id in engine.adapters():
+            return _adapter_card(model_id)
         if model_id != model_name:
-            return JSONResponse(status_code=404, content={"error": {
-                "message": f"model '{model_id}' not found"}})
+            return _not_found(model_id)
         return {"id": model_name, "object": "model",
                 "owned_by": "runbooks-amd"}
+
+    def _pick_model(requested: str):
+        """The request's ``model`` field -> (adapter or None, name served);
+        None when it names neither the base nor a loaded adapter."""
+        if not requested or requested == model_name:
+            return None, model_name
+        if requested in engine.adapters():
+            return requested, requested
+        return None
 
     def _usage(n_prompt, n_out):
         return {"prompt_tokens": n_prompt, "completion_tokens": n_out,
@@ -370,6 +433,10 @@ def build_app(engine: Engine, tokenizer=None,
         if len(engine.waiting) >= max_queue:
             return JSONResponse(status_code=429, content={"error": {
                 "message": "server overloaded: request queue full"}})
+        picked = _pick_model(req.model)
+        if picked is None:
+            return _not_found(req.model)
+        adapter, served = picked
         ids = _encode(req.prompt, req.max_tokens)
         cid = f"cmpl-{uuid.uuid4().hex[:12]}"
         t0 = int(time.time())
@@ -394,7 +461,8 @@ def build_app(engine: Engine, tokenizer=None,
                             frequency_penalty=req.frequency_penalty,
                             repetition_penalty=req.repetition_penalty,
                             stop_token_ids=eos_ids,
-                            top_k=req.top_k, min_p=req.min_p)
+                            top_k=req.top_k, min_p=req.min_p,
+                            adapter=adapter)
                 for i in range(n_sample)]
         q, ereq = subs[0]
 
@@ -402,7 +470,7 @@ def build_app(engine: Engine, tokenizer=None,
             def gen():
                 def chunk(text):
                     c = {"id": cid, "object": "text_completion",
-                         "created": t0, "model": req.model or model_name,
+                         "created": t0, "model": served,
                          "choices": [{"text": text, "index": 0,
                                       "logprobs": None,
                                       "finish_reason": None}]}
@@ -415,7 +483,7 @@ def build_app(engine: Engine, tokenizer=None,
                         yield chunk(piece)
                     fin = {"id": cid, "object": "text_completion",
                            "created": t0,
-                           "model": req.model or model_name,
+                           "model": served,
                            "choices": [{"text": "", "index": 0,
                                         "logprobs": None,
                                         "finish_reason": state["finish"]}]}
@@ -459,7 +527,7 @@ def build_app(engine: Engine, tokenizer=None,
             "id": cid,
             "object": "text_completion",
             "created": t0,
-            "model": req.model or model_name,
+            "model": served,
             "choices": choices,
             "usage": _usage(len(ids), n_out),
         })
@@ -475,7 +543,10 @@ def build_app(engine: Engine, tokenizer=None,
         prompt += "\nassistant:"
         cid = f"chatcmpl-{uuid.uuid4().hex[:12]}"
         t0 = int(time.time())
-        mdl = req.model or model_name
+        picked = _pick_model(req.model)
+        if picked is None:
+            return _not_found(req.model)
+        adapter, mdl = picked
 
         if req.stream:
             if req.n > 1:
@@ -491,7 +562,8 @@ def build_app(engine: Engine, tokenizer=None,
                                   frequency_penalty=req.frequency_penalty,
                                   repetition_penalty=req.repetition_penalty,
                                   stop_token_ids=eos_ids,
-                                  top_k=req.top_k, min_p=req.min_p)
+                                  top_k=req.top_k, min_p=req.min_p,
+                                  adapter=adapter)
 
             def gen():
                 def chunk(delta):

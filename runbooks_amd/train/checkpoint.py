@@ -19,7 +19,11 @@ from safetensors.torch import load_file, save_file
 
 def save_checkpoint(out_dir: str | Path, step: int, model_state: dict,
                     optim_state: dict | None = None, keep: int = 3,
-                    model_cfg=None) -> Path:
+                    model_cfg=None,
+                    extra_json: dict | None = None) -> Path:
+    """``extra_json``: {file name: json-able object} written into the
+    checkpoint before it is renamed into place, so a reader never sees
+    the directory without them."""
     out_dir = Path(out_dir)
     out_dir.mkdir(parents=True, exist_ok=True)
     ckpt = out_dir / f"checkpoint-{step}"
@@ -37,6 +41,8 @@ def save_checkpoint(out_dir: str | Path, step: int, model_state: dict,
         (tmp / "config.json").write_text(json.dumps({
             "runbooks_amd_config": model_cfg.name,
             "runbooks_amd_fields": dataclasses.asdict(model_cfg)}))
+    for fname, obj in (extra_json or {}).items():
+        (tmp / fname).write_text(json.dumps(obj))
     if ckpt.exists():
         import shutil
         shutil.rmtree(ckpt)

@@ -189,9 +189,15 @@ class Trainer:
             return
         state = (self.model.state_dict() if self.cfg.full_finetune
                  else lora_state_dict(self.model))
+        # adapter.json: what a Server needs to serve this adapter unmerged
+        # (serve/lora.py): the scale is alpha / r
+        extra = None if self.cfg.full_finetune else {
+            "adapter.json": {"lora_alpha": self.cfg.lora_alpha,
+                             "lora_r": self.cfg.lora_r}}
         ckpt_mod.save_checkpoint(self.cfg.output_dir, self.step_num, state,
                                  model_cfg=self.model.cfg,
-                                 optim_state=self.optimizer.state_dict())
+                                 optim_state=self.optimizer.state_dict(),
+                                 extra_json=extra)
 
     def resume(self) -> bool:
         """Resume model weights, optimizer moments, and the step counter

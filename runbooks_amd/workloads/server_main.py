@@ -17,6 +17,12 @@ examples/llama2-7b/server.yaml, container-contract.md:50-56) — loads
 - PARAM_BATCH_SAMPLER / BATCH_SAMPLER ("1" or "true"): sample each decode
   batch with the batched per-request sampler (one launch, one download);
   unset leaves the engine's RB_BATCH_SAMPLER default.
+- PARAM_LORA_ADAPTERS / LORA_ADAPTERS: LoRA adapters served over the one
+  base model, ``name=path,name=path`` (trainer adapter checkpoints or HF
+  PEFT directories); a bare directory loads each of its subdirectories
+  under its own name. A request picks one with its ``model`` field.
+  PARAM_MAX_LORAS / MAX_LORAS (default: the number listed) and
+  PARAM_LORA_RANK / LORA_RANK (default 16) size the adapter pool. TP=1.
 - TP: tensor parallelism degree (defaults to visible GPU count); ranks
   are spawned via torch.distributed.run over RCCL/xGMI.
 """
@@ -40,6 +46,36 @@ def _maybe_relaunch_tp() -> bool:
         f"--nproc-per-node={n}",
         "-m", "runbooks_amd.workloads.server_main"])
     return True
+
+
+def parse_lora_adapters(spec: str) -> list[tuple[str, Path]]:
+    """``name=path,name=path`` -> [(name, path)]; an entry without ``=``
+    is a directory whose subdirectories are adapters named after
+    themselves."""
+    out: list[tuple[str, Path]] = []
+    for item in (i.strip() for i in spec.split(",")):
+        if not item:
+            continue
+        if "=" in item:
+            name, path = item.split("=", 1)
+            out.append((name.strip(), Path(path.strip())))
+            continue
+        root = Path(item)
+        if not root.is_dir():
+            raise ValueError(f"LORA_ADAPTERS: {item} is neither name=path "
+                             f"nor a directory of adapters")
+        out.extend((p.name, p) for p in sorted(root.iterdir())
+                   if p.is_dir() and not p.name.startswith("."))
+    names = [n for n, _ in out]
+    dup = {n for n in names if names.count(n) > 1}
+    if dup or "" in names:
+        raise ValueError(f"LORA_ADAPTERS: empty or repeated adapter names "
+                         f"{sorted(dup)}")
+    return out
+
+
+def _env(name: str) -> str:
+    return os.environ.get(f"PARAM_{name}", os.environ.get(name, ""))
 
 
 def main():
@@ -119,13 +155,21 @@ def main():
     bsampler = os.environ.get(
         "PARAM_BATCH_SAMPLER",
         os.environ.get("BATCH_SAMPLER", "")).lower() in ("1", "true")
+    loras = parse_lora_adapters(_env("LORA_ADAPTERS"))
+    max_loras = int(_env("MAX_LORAS") or len(loras))
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
                     kv_fp8=kv_fp8, w4_resident=resident or None,
                     # unset leaves the engine's own RB_* env defaults
                     prefill_from_cache=from_cache or None,
                     prefill_chunk=chunk or None,
                     prefill_batch=pbatch or None,
-                    batch_sampler=bsampler or None)
+                    batch_sampler=bsampler or None,
+                    # unset / none listed leaves RB_MAX_LORAS, RB_LORA_RANK
+                    max_loras=max_loras or None,
+                    lora_rank=int(_env("LORA_RANK") or 0) or None)
+    for name, path in loras:
+        engine.load_adapter(name, path)
+        print(f"server: adapter {name!r} loaded from {path}")
     tok = load_tokenizer(model_dir if model_dir.exists() else None)
     if comm.rank() == 0:
         serve_forever(engine, tok, port=int(os.environ.get("PORT", "8080")),

@@ -69,6 +69,48 @@ min-p as value thresholds, then the draw. `RB_BATCH_SAMPLER=1`
 (`PARAM_BATCH_SAMPLER` on the server image) sends every batch that way;
 by default batches without `top_k` / `min_p` keep the older path, which
 applies `top_p` before the temperature.
+
+### LoRA adapters: the `model` field
+
+One server can serve many LoRA fine-tunes of its base model
+(`runbooks_amd/serve/lora.py`). `model` picks one per request:
+
+| `model` | served |
+|---|---|
+| missing, `""` or the base model's name | the base model |
+| the name of a loaded adapter | base + that adapter |
+| anything else | 404, `{"error": {"message": "model '<id>' not found"}}` |
+
+The response's `model` echoes what was served. `GET /v1/models` lists the
+base and every loaded adapter, adapters with `"parent": <base>`.
+
+Engine knobs (`Engine(..., max_loras=0, lora_rank=16)`; env `RB_MAX_LORAS`,
+`RB_LORA_RANK`; `PARAM_LORA_ADAPTERS` / `PARAM_MAX_LORAS` /
+`PARAM_LORA_RANK` on the server image, `docs/container-contract.md`):
+`max_loras` adapter slots of rank `lora_rank` (a multiple of 16, at most
+64) are preallocated per block and GEMM site; with the default 0 nothing
+is allocated and no code path changes. `engine.load_adapter(name, path)`
+reads a trainer adapter checkpoint (`checkpoint-N/`, or a directory of
+them: the latest; `lora_alpha` from its `adapter.json`, else 32) or an HF
+PEFT directory (`adapter_model.safetensors` + `adapter_config.json`) on
+q/k/v/o/gate/up/down projections; a smaller rank is zero-padded, a larger
+one, a shape that does not match the base or any other target is refused
+by name. `engine.unload_adapter(name)` is refused while a request uses the
+adapter; `engine.adapters()` lists the names; `submit(..., adapter=name)`
+raises `KeyError` for an unknown one. Both calls copy into memory the
+decode step reads: make them from the thread that steps the engine
+(`EngineLoop.load_adapter` / `unload_adapter` queue them there).
+
+A decode batch may mix adapters and adapter-free rows; a batch with at
+least one adapter row runs each GEMM site as the plain base GEMM plus
+`ops.lora_shrink` / `ops.lora_expand_` (`lora_serve.hip` in
+`docs/kernels.md`), under its own hipGraph family. Prefix-cache blocks
+are keyed on (adapter, tokens). Supported: TP=1; llama, mistral and gemma
+family models (fused qkv and gate-up); any base weight format (bf16,
+8-bit, 4-bit with or without `w4_resident`). Anything else raises
+`NotImplementedError` when the engine is built, and so does `max_loras >
+0` together with an fp8 KV cache: the engine refuses that combination at
+construction.
 """
 
 
