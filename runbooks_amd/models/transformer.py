@@ -160,6 +160,19 @@ class Attention(nn.Module):
             return self._o_lora(o.reshape(T, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(T, self.hq * self.dh))
 
+    def forward_verify(self, x, cos, sin, positions, kc, vc, slot_mapping,
+                       block_tables, seq_lens, q_lens, B, T, nsplit=None):
+        """Speculative verify: x [B*T, hidden], T rows per sequence. Append
+        every row's k/v (padding rows go to the dummy block), then attend
+        each sequence's real rows over its cache (ops.paged_verify). All
+        lengths stay on the device."""
+        q, k, v = self._qkv(x, cos, sin, positions)
+        ops.kv_append(k, v, kc, vc, slot_mapping)
+        o = ops.paged_verify(q.view(B, T, self.hq, self.dh), kc, vc,
+                             block_tables, seq_lens, q_lens,
+                             scale=self.scale, nsplit=nsplit)
+        return self.o_proj(o.reshape(B * T, self.hq * self.dh))
+
     def forward_decode(self, x, cos, sin, positions, kc, vc, slot_mapping,
                        block_tables, seq_lens, nsplit=None, slab_ok=False,
                        seq_starts=None, lora=None):
@@ -584,6 +597,33 @@ class Transformer(nn.Module):
                 block_tables, seq_lens, nsplit=nsplit, seq_starts=seq_starts,
                 lora=ll)
             x = blk(x, fn, lora=ll)
+        x = self.norm_f(x)
+        logits = self.lm_head(x)
+        return gather_from_tp(logits) if self._lm_vocab_parallel else logits
+
+    @torch.no_grad()
+    def verify(self, tokens, positions, caches, slot_mapping, block_tables,
+               seq_lens, q_lens, nsplit=None):
+        """Speculative verify step: tokens [B, T] hold, per sequence, its
+        last token followed by its drafts, at absolute ``positions``
+        [B, T]; ``q_lens`` (int32 [B], on the device) counts each
+        sequence's real rows and ``seq_lens`` its keys in the cache, these
+        rows included. Padding rows carry token 0, the position of the
+        row's last real token and a ``slot_mapping`` slot in the dummy
+        block. This is the packed-prefill forward with ops.paged_verify
+        as the attention; no length is read on the host, so the whole
+        call can be captured. Returns the logits of EVERY row [B*T, V]
+        (padding rows' are meaningless)."""
+        B, T = tokens.shape
+        positions = positions.reshape(-1)
+        slot_mapping = slot_mapping.reshape(-1)
+        x = self._embed(tokens, positions)
+        for blk, (kc, vc) in zip(self.blocks, caches):
+            fn = lambda h, b=blk, kc=kc, vc=vc: b.attn.forward_verify(  # noqa: E731
+                h, self.rope_cos, self.rope_sin, positions, kc, vc,
+                slot_mapping, block_tables, seq_lens, q_lens, B, T,
+                nsplit=nsplit)
+            x = blk(x, fn)
         x = self.norm_f(x)
         logits = self.lm_head(x)
         return gather_from_tp(logits) if self._lm_vocab_parallel else logits

@@ -11,7 +11,7 @@ from .attention import (causal_attention, flash_prefill, paged_decode,  # noqa: 
                         paged_decode_ref, paged_decode_with_operand,
                         paged_prefill, paged_prefill_batch,
                         paged_prefill_batch_ref, paged_prefill_plan,
-                        paged_prefill_ref)
+                        paged_prefill_ref, paged_verify, paged_verify_ref)
 from .kvcache import BLOCK_SIZE, alloc_kv_cache, kv_append, kv_append_ref  # noqa: F401
 from .linear import (Linear, decode_layout, decode_linear_glu,  # noqa: F401
                      decode_linear_raw, decode_linear_rope_append,

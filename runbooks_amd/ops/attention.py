@@ -341,6 +341,104 @@ def paged_prefill_batch(q, k_cache, v_cache, block_tables, plan,
                                    scale)
 
 
+VERIFY_MAX_T = 8
+
+
+def _check_verify_shapes(q, k_cache, block_tables, seq_lens, q_lens):
+    """Host-side checks of paged_verify: shapes and dtypes only, never a
+    length (those stay on the device)."""
+    if q.dim() != 4:
+        raise ValueError(f"paged_verify: q must be [B, T, Hq, Dh], got "
+                         f"{tuple(q.shape)}")
+    B, T, Hq, Dh = q.shape
+    if not 1 <= T <= VERIFY_MAX_T:
+        raise ValueError(f"paged_verify: T must be 1..{VERIFY_MAX_T}, got {T}")
+    if Hq % k_cache.shape[1]:
+        raise ValueError("paged_verify: Hq % Hkv")
+    if block_tables.dim() != 2 or block_tables.shape[0] < B:
+        raise ValueError(
+            f"paged_verify: block_tables {tuple(block_tables.shape)} has "
+            f"fewer rows than the {B} sequences")
+    for name, t in (("block_tables", block_tables), ("seq_lens", seq_lens),
+                    ("q_lens", q_lens)):
+        if t.dtype != torch.int32:
+            raise TypeError(f"paged_verify: {name} must be int32, got "
+                            f"{t.dtype}")
+    if seq_lens.dim() != 1 or q_lens.dim() != 1 or \
+            seq_lens.shape[0] < B or q_lens.shape[0] < B:
+        raise ValueError("paged_verify: seq_lens and q_lens must be [B]")
+
+
+def paged_verify_ref(q, k_cache, v_cache, block_tables, seq_lens, q_lens,
+                     scale=None):
+    """fp32 reference for paged_verify (and its CPU path):
+    paged_prefill_ref on each sequence's real rows with
+    ctx = seq_lens[b] - q_lens[b]; zeros in the padding rows. A sequence
+    with q_lens[b] == 0 reads nothing, not even its table row."""
+    if k_cache.dtype == torch.uint8:
+        raise NotImplementedError(
+            "paged_verify: fp8 KV caches are not supported")
+    _check_verify_shapes(q, k_cache, block_tables, seq_lens, q_lens)
+    out = torch.zeros_like(q)
+    for b in range(q.shape[0]):
+        n, s = int(q_lens[b]), int(seq_lens[b])
+        if n <= 0:
+            continue
+        out[b, :n] = paged_prefill_ref(q[b, :n], k_cache, v_cache,
+                                       block_tables[b], s - n, scale)
+    return out
+
+
+def verify_auto_nsplit(B: int, hkv: int, rows: int, max_blocks: int) -> int:
+    """Key split for paged_verify from host-known sizes only: aim at ~512
+    workgroups (the MFMA decode kernel's knee), at least 8 cache blocks
+    (128 keys) per split of the widest possible sequence, at most 16."""
+    tiles = (rows + 31) // 32 if rows > 16 else 1
+    base = max(1, B * hkv * tiles)
+    return max(1, min(16, 512 // base, (max_blocks + 7) // 8))
+
+
+def paged_verify(q, k_cache, v_cache, block_tables, seq_lens, q_lens,
+                 scale: float | None = None, nsplit: int | None = None):
+    """Multi-query decode attention over the paged cache: the attention of
+    a speculative verify step.
+
+    q [B, T, Hq, Dh] bf16, 1 <= T <= 8. Sequence b has ``seq_lens[b]`` keys
+    in the cache (its new ones included; they are appended before the call)
+    and ``q_lens[b]`` (0..T) real query rows: row t < q_lens[b] is the query
+    at position seq_lens[b] - q_lens[b] + t and attends to keys up to that
+    position. Rows t >= q_lens[b] are padding: they read nothing and are
+    returned as zeros; with q_lens[b] == 0 nothing of table row b is read.
+    block_tables, seq_lens and q_lens are int32 device tensors and are only
+    read on the device, so the launch can sit in a captured graph; ``nsplit``
+    (flash-decoding key split) is fixed per launch and defaults to a value
+    picked from B, Hkv and the table width. GPU: the gfx950 kernel
+    (csrc/attention_verify.hip), bf16 caches in either alloc_kv_cache
+    layout, Dh 64/128; fp8 caches and Dh 256 raise. CPU: fp32 reference.
+    """
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    if _backend.use_hip(q):
+        if k_cache.dtype == torch.uint8:
+            raise NotImplementedError(
+                "paged_verify: fp8 KV caches are not supported")
+        if q.shape[-1] not in (64, 128):
+            raise NotImplementedError(
+                f"paged_verify: head_dim must be 64 or 128 on the GPU, got "
+                f"{q.shape[-1]}")
+        _check_verify_shapes(q, k_cache, block_tables, seq_lens, q_lens)
+        if nsplit is None:
+            hkv = k_cache.shape[1]
+            nsplit = verify_auto_nsplit(
+                q.shape[0], hkv, (q.shape[2] // hkv) * q.shape[1],
+                block_tables.shape[1])
+        return _backend.ext().paged_verify(
+            q.contiguous(), k_cache, v_cache, block_tables, seq_lens, q_lens,
+            int(nsplit), float(scale))
+    return paged_verify_ref(q, k_cache, v_cache, block_tables, seq_lens,
+                            q_lens, scale)
+
+
 def _is_vt(k_cache, v_cache) -> bool:
     """Transposed-V cache layout (alloc_kv_cache v_transposed) == the
     MFMA decode path; the shape is the routing signal. fp8 vt blocks

@@ -52,6 +52,9 @@ std::vector<at::Tensor> paged_decode_swz(at::Tensor q, at::Tensor k_cache,
                                          at::Tensor seq_lens, int64_t nsplit,
                                          double scale,
                                          c10::optional<at::Tensor> seq_starts);
+at::Tensor paged_verify(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
+                        at::Tensor block_tables, at::Tensor seq_lens,
+                        at::Tensor q_lens, int64_t nsplit, double scale);
 at::Tensor flash_prefill(at::Tensor q, at::Tensor k, at::Tensor v, double scale);
 at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                                at::Tensor block_table, int64_t ctx_len, double scale);
@@ -164,6 +167,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("nsplit"),
         py::arg("scale"), py::arg("seq_starts") = py::none());
+  m.def("paged_verify", &paged_verify,
+        "multi-query paged decode attention (speculative verify): up to 8 "
+        "query rows per sequence, all lengths on the device",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_tables"), py::arg("seq_lens"), py::arg("q_lens"),
+        py::arg("nsplit"), py::arg("scale"));
   m.def("flash_prefill", &flash_prefill, "MFMA flash-attention prefill (causal)");
   m.def("flash_prefill_paged", &flash_prefill_paged,
         "MFMA flash-attention prefill of one chunk over the paged KV cache",

@@ -4,6 +4,7 @@
 pure-engine users).
 """
 from .engine import BlockAllocator, Engine, Request  # noqa: F401
+from .spec import NgramDrafter  # noqa: F401
 from .tokenizer import ByteTokenizer, load_tokenizer  # noqa: F401
 
 

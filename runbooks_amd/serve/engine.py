@@ -127,7 +127,10 @@ class Engine:
                  w4_resident: bool | None = None,
                  batch_sampler: bool | None = None,
                  max_loras: int | None = None,
-                 lora_rank: int | None = None):
+                 lora_rank: int | None = None,
+                 speculative: int | None = None,
+                 spec_ngram: int | None = None,
+                 drafter=None):
         self.device = device if device is not None else (
             f"cuda:{comm.local_rank()}" if torch.cuda.is_available() else "cpu")
         if isinstance(model, str):
@@ -345,6 +348,44 @@ class Engine:
         if self.lora_pool is not None:
             self.stats["lora_decode_steps"] = 0
             self.stats["lora_rows"] = 0
+        # Speculative decoding (off by default): RB_SPECULATIVE=K /
+        # speculative=K in 1..7 drafts up to K tokens per running sequence
+        # per step from the request's own text (serve/spec.py NgramDrafter
+        # over RB_SPEC_NGRAM / spec_ngram tokens, or ``drafter``) and
+        # verifies them in one forward (Transformer.verify,
+        # ops/csrc/attention_verify.hip). Every row is sampled with the
+        # batched sampler at the seed its position would get without
+        # speculation, so the text is that of Engine(batch_sampler=True);
+        # the knob therefore also turns the batched sampler on. With 0
+        # nothing is allocated and every path is the one above.
+        K = int(speculative if speculative is not None
+                else _os.environ.get("RB_SPECULATIVE", "0") or 0)
+        N = int(spec_ngram if spec_ngram is not None
+                else _os.environ.get("RB_SPEC_NGRAM", "3") or 3)
+        if not 0 <= K <= ops.attention.VERIFY_MAX_T - 1:
+            raise ValueError(f"speculative must be 0.."
+                             f"{ops.attention.VERIFY_MAX_T - 1}, got {K}")
+        if K > 0:
+            why = ("at TP>1" if self.tp > 1 or model.tp > 1
+                   else "with an fp8 KV cache" if self.kv_fp8
+                   else "for a sliding-window model"
+                   if self.cfg.sliding_window
+                   else "at head_dim 256" if self.cfg.head_dim not in (64, 128)
+                   else None)
+            if why is not None:
+                print(f"engine: speculative ignored {why} (the verify "
+                      "kernel is single-GPU bf16, head_dim 64/128, full "
+                      "attention; one token per step is used)", flush=True)
+                K = 0
+        self.speculative = K
+        self.drafter = None
+        if K > 0:
+            if drafter is None:
+                from .spec import NgramDrafter
+                drafter = NgramDrafter(N)
+            self.drafter = drafter
+            self.batch_sampler = True
+            self.stats.update(spec_steps=0, spec_drafted=0, spec_accepted=0)
 
     def _auto_kv_blocks(self, mem_fraction: float) -> int:
         elem = (self.cfg.head_dim + 16) if self.kv_fp8 \
@@ -749,6 +790,15 @@ class Engine:
         self.stats["prefill_batched_requests"] += len(reqs)
         return first
 
+    def _graph_decoder(self):
+        """The engine's GraphedDecoder, built on first use."""
+        if self._graphed is None:
+            from .graph import GraphedDecoder
+            self._graphed = GraphedDecoder(
+                self.model, self.caches, self.max_batch,
+                self.max_blocks_per_seq, self.dummy_block, self.device)
+        return self._graphed
+
     def _decode_batch(self, reqs: list[Request]) -> list[int]:
         B = len(reqs)
         dev = self.device
@@ -776,12 +826,7 @@ class Engine:
                 self._decode_lora(reqs, last, pos, slots, vpos, starts),
                 reqs)
         if self.use_graphs and B <= self.max_batch:
-            if self._graphed is None:
-                from .graph import GraphedDecoder
-                self._graphed = GraphedDecoder(
-                    self.model, self.caches, self.max_batch,
-                    self.max_blocks_per_seq, self.dummy_block, dev)
-            logits = self._graphed.decode(last, pos, slots,
+            logits = self._graph_decoder().decode(last, pos, slots,
                                           [r.blocks for r in reqs],
                                           [v + 1 for v in vpos], starts)
         else:
@@ -815,14 +860,10 @@ class Engine:
         self.stats["lora_decode_steps"] += 1
         self.stats["lora_rows"] += sum(1 for s in lslots if s >= 0)
         if self.use_graphs and B <= self.max_batch:
-            if self._graphed is None:
-                from .graph import GraphedDecoder
-                self._graphed = GraphedDecoder(
-                    self.model, self.caches, self.max_batch,
-                    self.max_blocks_per_seq, self.dummy_block, dev)
-            if self._graphed.lora_pool is None:
-                self._graphed.enable_lora(self.lora_pool)
-            return self._graphed.decode(last, pos, slots,
+            gd = self._graph_decoder()
+            if gd.lora_pool is None:
+                gd.enable_lora(self.lora_pool)
+            return gd.decode(last, pos, slots,
                                         [r.blocks for r in reqs],
                                         [v + 1 for v in vpos], starts,
                                         adapter_slots=lslots)
@@ -839,6 +880,117 @@ class Engine:
                          device=dev),
             seq_starts=torch.tensor(starts, dtype=torch.int32, device=dev),
             lora=LoraBatch(self.lora_pool, lslots))
+
+    def _spec_decode(self, reqs: list[Request]) -> list[list[int]] | None:
+        """One speculative step over the running batch: draft, verify in
+        one forward, sample every row, accept the agreeing prefix. Returns
+        each request's emitted tokens (one or more), or None when the step
+        has to take the normal path: no row has a draft, or a row has an
+        adapter."""
+        if any(r.adapter is not None for r in reqs):
+            return None
+        K, bs = self.speculative, self.bs
+        free = len(self.allocator.free)
+        drafts: list[list[int]] = []
+        for r in reqs:
+            L = r.seq_len
+            n = min(K, r.max_new_tokens - len(r.output_ids) - 1,
+                    self.cfg.max_seq_len - 1 - L)
+            if (r.presence_penalty or r.frequency_penalty
+                    or r.repetition_penalty != 1.0
+                    or r.logprobs is not None):
+                n = 0
+            d = [int(t) for t in self.drafter.propose(r, n)][:n] \
+                if n > 0 else []
+            # a drafter is user code: an id outside the vocabulary would
+            # index the embedding out of bounds, so the draft ends there
+            V = self.cfg.vocab_size
+            for j, t in enumerate(d):
+                if not 0 <= t < V:
+                    d = d[:j]
+                    break
+            # blocks for positions L-1 .. L-1+len(d) must be free NOW:
+            # a draft never evicts or preempts
+            while d and (L - 1 + len(d)) // bs + 1 - len(r.blocks) > free:
+                d.pop()
+            if d:
+                need = (L - 1 + len(d)) // bs + 1 - len(r.blocks)
+                if need > 0:
+                    r.blocks.extend(self.allocator.alloc(need))
+                    free -= need
+            drafts.append(d)
+        if not any(drafts):
+            return None
+        dev = self.device
+        tok_rows, pos_rows, slot_rows = [], [], []
+        for r, d in zip(reqs, drafts):
+            L = r.seq_len
+            last = r.output_ids[-1] if r.output_ids else r.prompt_ids[-1]
+            tok_rows.append([last] + d)
+            pos_rows.append(list(range(L - 1, L + len(d))))
+            slot_rows.append([r.blocks[p // bs] * bs + p % bs
+                              for p in pos_rows[-1]])
+        seq_lens = [r.seq_len + len(d) for r, d in zip(reqs, drafts)]
+        B = len(reqs)
+        if self.use_graphs and B <= self.max_batch:
+            gd = self._graph_decoder()
+            if gd.verify_T is None:
+                gd.enable_verify(K + 1)
+            T = K + 1
+            logits = gd.verify(tok_rows, pos_rows, slot_rows,
+                                          [r.blocks for r in reqs], seq_lens)
+        else:
+            T = 1 + max(len(d) for d in drafts)
+            maxb = max(len(r.blocks) for r in reqs)
+            bt = torch.full((B, maxb), self.dummy_block, dtype=torch.int32)
+            for i, r in enumerate(reqs):
+                bt[i, :len(r.blocks)] = torch.tensor(r.blocks,
+                                                     dtype=torch.int32)
+            pad_slot = self.dummy_block * bs
+            tokens = [t + [0] * (T - len(t)) for t in tok_rows]
+            poss = [p + [p[-1]] * (T - len(p)) for p in pos_rows]
+            slots = [s + [pad_slot] * (T - len(s)) for s in slot_rows]
+            logits = self.model.verify(
+                torch.tensor(tokens, dtype=torch.long, device=dev),
+                torch.tensor(poss, dtype=torch.int32, device=dev),
+                self.caches,
+                torch.tensor(slots, dtype=torch.int32, device=dev),
+                bt.to(dev),
+                torch.tensor(seq_lens, dtype=torch.int32, device=dev),
+                torch.tensor([len(t) for t in tok_rows], dtype=torch.int32,
+                             device=dev))
+        # every real row is sampled at the seed its position would get in a
+        # step of its own
+        idx, owners, seed_pos = [], [], []
+        for i, (r, d) in enumerate(zip(reqs, drafts)):
+            for j in range(len(d) + 1):
+                idx.append(i * T + j)
+                owners.append(r)
+                seed_pos.append(r.seq_len + j)
+        if len(idx) != logits.shape[0]:
+            logits = logits.index_select(
+                0, torch.tensor(idx, dtype=torch.long, device=dev))
+        sampled = self._sample_batched(logits, owners, seed_pos)
+        out: list[list[int]] = []
+        k = 0
+        self.stats["spec_steps"] += 1
+        for r, d in zip(reqs, drafts):
+            s = sampled[k:k + len(d) + 1]
+            k += len(d) + 1
+            a = 0
+            while a < len(d) and s[a] == d[a]:
+                a += 1
+            # the drafts were trimmed to max_new_tokens above, so the run
+            # fits; a stop id inside it ends it there
+            emit = s[:a + 1]
+            for j, t in enumerate(emit):
+                if r.stop_ids and t in r.stop_ids:
+                    emit = emit[:j + 1]
+                    break
+            self.stats["spec_drafted"] += len(d)
+            self.stats["spec_accepted"] += len(emit) - 1
+            out.append(emit)
+        return out
 
     def _use_batch_sampler(self, reqs: list[Request]) -> bool:
         return self.batch_sampler or any(r.top_k > 0 or r.min_p > 0.0
@@ -863,11 +1015,14 @@ class Engine:
         ent["out"] = n_o
         return cnt
 
-    def _sample_batched(self, logits, reqs: list[Request]) -> list[int]:
+    def _sample_batched(self, logits, reqs: list[Request],
+                        seed_pos: list[int] | None = None) -> list[int]:
         """One ops.sample_batch call and one download for the whole
-        batch, each row with its own parameters and seed."""
+        batch, each row with its own parameters and seed. ``seed_pos``
+        (speculative verify: a request may own several rows) gives each
+        row's sequence length for the seed instead of ``r.seq_len``."""
         rows, counts = [], []
-        for r in reqs:
+        for i, r in enumerate(reqs):
             base = (r.seed * 2654435761 if r.seed is not None
                     else self.seed + r.request_id * 65537)
             rows.append({"temperature": r.temperature, "top_k": r.top_k,
@@ -875,7 +1030,8 @@ class Engine:
                          "presence": r.presence_penalty,
                          "frequency": r.frequency_penalty,
                          "repetition": r.repetition_penalty,
-                         "seed": base + r.seq_len})
+                         "seed": base + (r.seq_len if seed_pos is None
+                                         else seed_pos[i])})
             pen = (r.presence_penalty or r.frequency_penalty
                    or r.repetition_penalty != 1.0)
             counts.append(self._token_counts(r) if pen else None)
@@ -971,6 +1127,7 @@ class Engine:
             if r.request_id == request_id:
                 self.waiting.remove(r)
                 r.finished = True
+                self._forget(r)
                 return True
         r = self.prefilling
         if r is not None and r.request_id == request_id:
@@ -978,6 +1135,7 @@ class Engine:
             self.allocator.release(r.blocks)
             r.blocks = []
             r.finished = True
+            self._forget(r)
             return True
         for r in self.running:
             if r.request_id == request_id:
@@ -1104,16 +1262,36 @@ class Engine:
                         self._preempt(r)
                         break
             if self.running:
-                if tr:
-                    with tr.span("decode", batch=len(self.running)):
-                        toks = self._decode_batch(self.running)
+                spec = None
+                if self.speculative:
+                    if tr:
+                        with tr.span("spec_decode", batch=len(self.running)):
+                            spec = self._spec_decode(self.running)
+                    else:
+                        spec = self._spec_decode(self.running)
+                if spec is not None:
+                    # several tokens per request from one forward
+                    for r, ts in zip(self.running, spec):
+                        r.output_ids.extend(ts)
+                        self.stats["decode_tokens"] += len(ts)
                 else:
-                    toks = self._decode_batch(self.running)
-                self.stats["decode_tokens"] += len(toks)
-                for r, t in zip(self.running, toks):
-                    r.output_ids.append(t)
+                    if tr:
+                        with tr.span("decode", batch=len(self.running)):
+                            toks = self._decode_batch(self.running)
+                    else:
+                        toks = self._decode_batch(self.running)
+                    self.stats["decode_tokens"] += len(toks)
+                    for r, t in zip(self.running, toks):
+                        r.output_ids.append(t)
         self._sweep_finished(finished)
         return finished
+
+    def _forget(self, r: Request) -> None:
+        """Drop the per-request state kept outside the request (penalty
+        token counts, the drafter's index) when it leaves the engine."""
+        self._tok_counts.pop(r.request_id, None)
+        if self.drafter is not None and hasattr(self.drafter, "forget"):
+            self.drafter.forget(r.request_id)
 
     def _sweep_finished(self, finished: list[Request]) -> None:
         for r in list(self.running):
@@ -1124,7 +1302,7 @@ class Engine:
                 self.allocator.release(r.blocks)
                 r.blocks = []
                 self.running.remove(r)
-                self._tok_counts.pop(r.request_id, None)
+                self._forget(r)
                 finished.append(r)
 
     def has_work(self) -> bool:

@@ -69,6 +69,7 @@ class GraphedDecoder:
         self.graphs = {}     # bucket -> (CUDAGraph, logits_out)
         self._pool = None
         self.lora_pool = None   # serve/lora.py AdapterPool (enable_lora)
+        self.verify_T = None    # rows per sequence of the verify family
 
     def enable_lora(self, pool) -> None:
         """Second graph family, keyed (bucket, "lora"), for batches in
@@ -84,6 +85,140 @@ class GraphedDecoder:
         self.h_adapter = torch.full((B,), -1, dtype=torch.int32,
                                     pin_memory=torch.cuda.is_available())
         self._np_adapter = self.h_adapter.numpy()
+
+    def enable_verify(self, T: int, vocab_size: int | None = None) -> None:
+        """Third graph family, keyed (bucket, "verify"): the speculative
+        verify forward (Transformer.verify) at a fixed T rows per sequence
+        and a fixed key split. Static buffers of its own hold tokens,
+        positions and slots [B, T], seq_lens and q_lens [B]; the block
+        tables are the decode family's buffer. Filled from a pinned staging
+        tensor of its own; the other families are untouched."""
+        B = self.tokens.shape[0]
+        dev = self.device
+        self.verify_T = int(T)
+        # staged token ids are checked against it (the model's, unless given)
+        self.vocab_size = int(vocab_size if vocab_size is not None
+                              else self.model.cfg.vocab_size)
+        self.v_tokens = torch.zeros(B, T, dtype=torch.long, device=dev)
+        self.v_positions = torch.zeros(B, T, dtype=torch.int32, device=dev)
+        self.v_slots = torch.full((B, T), self.dummy_block * _bs(),
+                                  dtype=torch.int32, device=dev)
+        self.v_seq_lens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.v_q_lens = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.h_verify = torch.zeros(
+            B * (3 * T + 2) + B * self.max_blocks, dtype=torch.int64,
+            pin_memory=torch.cuda.is_available())
+        self._np_verify = self.h_verify.numpy()
+
+    def _verify_nsplit(self, b: int) -> int:
+        from ..ops.attention import verify_auto_nsplit
+        attn = self.model.blocks[0].attn
+        return verify_auto_nsplit(b, attn.hkv,
+                                  (attn.hq // attn.hkv) * self.verify_T,
+                                  self.max_blocks)
+
+    def _capture_verify(self, b: int):
+        args = (self.v_tokens[:b], self.v_positions[:b], self.caches,
+                self.v_slots[:b], self.block_tables[:b],
+                self.v_seq_lens[:b], self.v_q_lens[:b])
+        kw = dict(nsplit=self._verify_nsplit(b))
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                self.model.verify(*args, **kw)
+        torch.cuda.current_stream().wait_stream(s)
+
+        g = torch.cuda.CUDAGraph()
+        if self._pool is None:
+            with torch.cuda.graph(g):
+                out = self.model.verify(*args, **kw)
+            self._pool = g.pool()
+        else:
+            with torch.cuda.graph(g, pool=self._pool):
+                out = self.model.verify(*args, **kw)
+        self.graphs[(b, "verify")] = (g, out)
+
+    def verify(self, token_rows, pos_rows, slot_rows, block_rows, seq_lens):
+        """Replay the verify family. Host lists: sequence i brings
+        len(token_rows[i]) (1..T) real rows with their positions and slots,
+        its block list and its key count. Returns logits [n * T, V] (a view
+        into the static output), row i * T + j for row j of sequence i."""
+        n = len(token_rows)
+        b = next(x for x in self.buckets if x >= n)
+        self._stage_verify(b, token_rows, pos_rows, slot_rows, block_rows,
+                           seq_lens)
+        if (b, "verify") not in self.graphs:
+            self._capture_verify(b)
+        g, out = self.graphs[(b, "verify")]
+        T, mb, h = self.verify_T, self.max_blocks, self.h_verify
+        bT = b * T
+        self.v_tokens[:b].copy_(h[0:bT].view(b, T), non_blocking=True)
+        self.v_positions[:b].copy_(h[bT:2 * bT].view(b, T),
+                                   non_blocking=True)
+        self.v_slots[:b].copy_(h[2 * bT:3 * bT].view(b, T),
+                               non_blocking=True)
+        o = 3 * bT
+        self.v_seq_lens[:b].copy_(h[o:o + b], non_blocking=True)
+        self.v_q_lens[:b].copy_(h[o + b:o + 2 * b], non_blocking=True)
+        self.block_tables[:b].copy_(
+            h[o + 2 * b:o + 2 * b + b * mb].view(b, mb), non_blocking=True)
+        g.replay()
+        return out[:n * T]
+
+    def _stage_verify(self, b, token_rows, pos_rows, slot_rows, block_rows,
+                      seq_lens) -> None:
+        """Range-check the step's lengths, token ids, slots and block ids on
+        the host (the kernels only index with them) and fill the pinned staging
+        buffer for bucket b. Padding rows of a sequence repeat its last
+        position, carry token 0 and write to the dummy block; sequences
+        beyond n have q_len 0 and are not read at all. CPU-testable."""
+        n = len(token_rows)
+        T, mb, bs = self.verify_T, self.max_blocks, _bs()
+        nblk = self.caches[0][0].shape[0]
+        hn = self._np_verify
+        bT = b * T
+        tok = hn[0:bT].reshape(b, T)
+        pos = hn[bT:2 * bT].reshape(b, T)
+        slt = hn[2 * bT:3 * bT].reshape(b, T)
+        o = 3 * bT
+        sl = hn[o:o + b]
+        ql = hn[o + b:o + 2 * b]
+        btn = hn[o + 2 * b:o + 2 * b + b * mb].reshape(b, mb)
+        for i in range(n):
+            q = len(token_rows[i])
+            s = int(seq_lens[i])
+            row = block_rows[i]
+            if not (1 <= q <= T and len(pos_rows[i]) == q
+                    and len(slot_rows[i]) == q):
+                raise ValueError(f"verify row {i}: {q} query rows, the graph "
+                                 f"holds 1..{T}")
+            if not (q <= s <= len(row) * bs and len(row) <= mb):
+                raise ValueError(f"verify row {i}: seq_len {s} with {q} rows "
+                                 f"and {len(row)} blocks (table width {mb})")
+            V = self.vocab_size
+            if any(not 0 <= x < V for x in token_rows[i]):
+                raise ValueError(f"verify row {i}: token id outside the "
+                                 f"vocabulary of {V}")
+            if any(not 0 <= x < nblk for x in row) or \
+                    any(not 0 <= x < nblk * bs for x in slot_rows[i]):
+                raise ValueError(f"verify row {i}: block id or slot out of "
+                                 f"the pool of {nblk} blocks")
+        tok.fill(0)
+        pos.fill(0)
+        slt.fill(self.dummy_block * bs)
+        sl.fill(0)
+        ql.fill(0)
+        btn.fill(self.dummy_block)
+        for i in range(n):
+            q = len(token_rows[i])
+            tok[i, :q] = token_rows[i]
+            pos[i, :q] = pos_rows[i]
+            pos[i, q:] = pos_rows[i][-1]
+            slt[i, :q] = slot_rows[i]
+            sl[i] = seq_lens[i]
+            ql[i] = q
+            btn[i, :len(block_rows[i])] = block_rows[i]
 
     # -- capture -----------------------------------------------------------
     def _capture(self, b: int, lora: bool = False):

@@ -17,6 +17,10 @@ examples/llama2-7b/server.yaml, container-contract.md:50-56) — loads
 - PARAM_BATCH_SAMPLER / BATCH_SAMPLER ("1" or "true"): sample each decode
   batch with the batched per-request sampler (one launch, one download);
   unset leaves the engine's RB_BATCH_SAMPLER default.
+- PARAM_SPECULATIVE / SPECULATIVE (K in 1..7): speculative decoding with
+  up to K n-gram drafts per sequence per step, verified in one forward;
+  PARAM_SPEC_NGRAM / SPEC_NGRAM (default 3) is the longest suffix matched.
+  Unset leaves the engine's RB_SPECULATIVE / RB_SPEC_NGRAM defaults (off).
 - PARAM_LORA_ADAPTERS / LORA_ADAPTERS: LoRA adapters served over the one
   base model, ``name=path,name=path`` (trainer adapter checkpoints or HF
   PEFT directories); a bare directory loads each of its subdirectories
@@ -155,6 +159,11 @@ def main():
     bsampler = os.environ.get(
         "PARAM_BATCH_SAMPLER",
         os.environ.get("BATCH_SAMPLER", "")).lower() in ("1", "true")
+    # PARAM_SPECULATIVE / SPECULATIVE: n-gram drafts verified per step
+    # (unset leaves RB_SPECULATIVE); PARAM_SPEC_NGRAM / SPEC_NGRAM: the
+    # longest suffix the drafter matches
+    spec_k = int(_env("SPECULATIVE") or 0)
+    spec_n = int(_env("SPEC_NGRAM") or 0)
     loras = parse_lora_adapters(_env("LORA_ADAPTERS"))
     max_loras = int(_env("MAX_LORAS") or len(loras))
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
@@ -164,6 +173,8 @@ def main():
                     prefill_chunk=chunk or None,
                     prefill_batch=pbatch or None,
                     batch_sampler=bsampler or None,
+                    speculative=spec_k or None,
+                    spec_ngram=spec_n or None,
                     # unset / none listed leaves RB_MAX_LORAS, RB_LORA_RANK
                     max_loras=max_loras or None,
                     lora_rank=int(_env("LORA_RANK") or 0) or None)

@@ -70,6 +70,30 @@ min-p as value thresholds, then the draw. `RB_BATCH_SAMPLER=1`
 by default batches without `top_k` / `min_p` keep the older path, which
 applies `top_p` before the temperature.
 
+### Speculative decoding
+
+`Engine(..., speculative=K, spec_ngram=3, drafter=None)` (env
+`RB_SPECULATIVE`, `RB_SPEC_NGRAM`; `PARAM_SPECULATIVE` / `PARAM_SPEC_NGRAM`
+on the server image) lets one engine step emit several tokens per request:
+each running request brings up to `K` (1..7) draft tokens, one forward
+(`Transformer.verify`, `attention_verify.hip` in `docs/kernels.md`) scores
+the request's last token and its drafts, every row is sampled by
+`ops.sample_batch` with the seed its position would get in a step of its
+own, and drafts are kept while they equal the sample. Given equal logits
+the completion is token for token that of `batch_sampler=True` without
+speculation, greedy or seeded; no request field changes. Streaming
+delivers every token of a step, in order. A `drafter` is any object with
+`propose(request, k) -> list[int]` (at most `k` tokens; an optional
+`forget(request_id)` is called when the request leaves); the default
+`NgramDrafter(spec_ngram)` proposes what followed the most recent earlier
+occurrence of the request's last `spec_ngram` (down to 1) tokens in its own
+prompt and output. Requests with a penalty or `logprobs` are served without
+drafts, a batch with an adapter row takes the normal step. `K = 0`
+(default) allocates nothing and changes no path; the knob is ignored with
+one printed line at TP>1, with an fp8 KV cache, for sliding-window models
+and at head_dim 256. `engine.stats` adds `spec_steps`, `spec_drafted` and
+`spec_accepted`.
+
 ### LoRA adapters: the `model` field
 
 One server can serve many LoRA fine-tunes of its base model
