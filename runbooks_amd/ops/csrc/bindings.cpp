@@ -78,7 +78,7 @@ at::Tensor mfma_probe_16x16x32(at::Tensor a, at::Tensor b);
 at::Tensor train_gemm_nt(at::Tensor a, at::Tensor b);
 at::Tensor skinny_gemm(at::Tensor x, at::Tensor w);
 at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K, int64_t force_split,
-                       int64_t layout, int64_t hq, int64_t hkv, int64_t dh);
+                       int64_t layout, int64_t hq, int64_t hkv, int64_t dh, int64_t u);
 at::Tensor decode_swizzle_w(at::Tensor w);
 at::Tensor decode_swizzle_x(at::Tensor x);
 int64_t decode_gemm_split(int64_t N, int64_t K);
@@ -204,7 +204,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "y[M<=32,N] = x @ W^T (bf16), 1KiB coalesced nt weight bursts",
         py::arg("xs"), py::arg("ws"), py::arg("M"), py::arg("N"),
         py::arg("K"), py::arg("force_split") = -1, py::arg("layout") = 0,
-        py::arg("hq") = 0, py::arg("hkv") = 0, py::arg("dh") = 0);
+        py::arg("hq") = 0, py::arg("hkv") = 0, py::arg("dh") = 0,
+        py::arg("u") = 0);
   m.def("decode_swizzle_w", &decode_swizzle_w,
         "one-time [N,K] -> fragment-lane-major weight layout");
   m.def("decode_swizzle_x", &decode_swizzle_x,

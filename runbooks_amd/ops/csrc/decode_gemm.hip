@@ -534,9 +534,11 @@ at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M,
 // xs from decode_swizzle_x, ws from decode_swizzle_w(_layout); M/N/K of
 // the ORIGINAL y[M,N] = x[M,K] @ W[N,K]^T problem. y is row-major in the
 // original column order whatever the weight layout.
+// u picks the k-steps per ring half: 0 = the default 8, 12 = the deeper
+// ring that RB_DG_U=12 gives the raw/fused entry points.
 at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
                        int64_t K, int64_t force_split, int64_t layout,
-                       int64_t hq, int64_t hkv, int64_t dh) {
+                       int64_t hq, int64_t hkv, int64_t dh, int64_t u) {
   TORCH_CHECK(xs.is_cuda() && ws.is_cuda() && xs.is_contiguous() &&
               ws.is_contiguous(), "decode_gemm: contiguous GPU tensors");
   TORCH_CHECK(xs.scalar_type() == at::kBFloat16 &&
@@ -545,6 +547,10 @@ at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
   TORCH_CHECK(ws.numel() == N * K, "decode_gemm: ws size");
   TORCH_CHECK(decode_gemm_supported(M, N, K),
               "decode_gemm: unsupported shape ", M, "x", N, "x", K);
+  TORCH_CHECK(force_split <= 8, "decode_gemm: force_split <= 8");
+  TORCH_CHECK(u == 0 || u == 12, "decode_gemm: u must be 0 (8) or 12, got ",
+              u);
+  const int ring = u == 12 ? 12 : 8;
   const EpiArgs ep = layout_args(layout, N, hq, hkv, dh);
 
   auto stream = at::cuda::getCurrentHIPStream();
@@ -552,11 +558,11 @@ at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
   const int split = force_split > 0 ? (int)force_split
                                     : (int)decode_gemm_split(N, K);
   if (split == 1) {
-    launch_dg_store<true>(layout, 8, 1, stream, xs, ws,
+    launch_dg_store<true>(layout, ring, 1, stream, xs, ws,
                           (uint16_t *)y.data_ptr(), nullptr, M, N, K, ep);
   } else {
     auto slabs = at::empty({split, M, N}, xs.options().dtype(at::kFloat));
-    launch_dg_store<false>(layout, 8, split, stream, xs, ws, nullptr,
+    launch_dg_store<false>(layout, ring, split, stream, xs, ws, nullptr,
                            (float *)slabs.data_ptr(), M, N, K, ep);
     const int64_t mn = M * N;
     const int grid = rb::rb_grid_1d(mn / 4, 256);
