@@ -103,9 +103,69 @@ def w4_gemm_rows(out, dev="cuda"):
         del ws, q4
 
 
+def dg_tail_rows(out, dev="cuda"):
+    """decode_gemm / decode_gemm_w4 with the K tail through the ring
+    (tail=1) against the one-step tail loop (tail=0), at the llama2-7b
+    split-K shapes. down-proj (K = 11008, split 2: 86 k-steps per wave =
+    80 ring + 6 tail) is the shape the ring tail is for; o_proj (32 steps
+    per wave, no tail) is the control: a launch in which no wave has a
+    tail runs the one-step-tail instantiation whatever `tail` says
+    (dg_has_tail / w4_has_tail), so its two rows time the same binary and
+    show the noise of the method. As for the decode norm above, each
+    variant is captured as a graph of 40 launches over ten rotating
+    weights (>= 335 MB, past the Infinity Cache) and the replays are timed
+    alternately, three rounds; the median round is reported. The rows time
+    the decode_gemm entry point, which at these splits also allocates the
+    slabs and launches the combine kernel; the decode loop's down-proj
+    goes through decode_gemm_raw and has neither. Both variants pay the
+    same, so the difference is the kernel's; the absolute us and GB/s are
+    not those of the kernel alone (profiles/README.md has them)."""
+    from runbooks_amd.ops.linear import quantize_int4
+    bf16 = torch.bfloat16
+    e = ops.ext()
+    for name, N, K in (("o_proj", 4096, 4096), ("down", 4096, 11008)):
+        ws = [torch.randn(N, K, dtype=bf16, device=dev) * 0.02
+              for _ in range(10)]
+        sx = e.decode_swizzle_x(torch.randn(32, K, dtype=bf16, device=dev))
+        sws = [e.decode_swizzle_w(w) for w in ws]
+        n4 = 20 if K == 4096 else 10
+        q4 = [e.w4_swizzle(*quantize_int4(ws[j % 10].roll(j // 10, 0)))
+              for j in range(n4)]
+        del ws
+        variants = {
+            "decode_gemm": (lambda j, t: e.decode_gemm(
+                sx, sws[j % 10], 32, N, K, tail=t), N * K * 2),
+            "decode_gemm_w4": (lambda j, t: e.decode_gemm_w4(
+                sx, *q4[j % n4], 32, N, K, tail=t),
+                N * K // 2 + N * K // 64 * 2),
+        }
+        for kern, (call, nbytes) in variants.items():
+            graphs = {}
+            for t in (0, 1):
+                call(0, t)
+                torch.cuda.synchronize()
+                graphs[t] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[t]):
+                    for j in range(40):
+                        call(j, t)
+            us = {0: [], 1: []}
+            for _ in range(3):
+                for t in (0, 1):
+                    us[t].append(timeit(graphs[t].replay, iters=20,
+                                        warmup=5) / 40)
+            for t in (0, 1):
+                out.append(row(f"{kern} {name} tail={t}", f"32x{N}x{K}",
+                               sorted(us[t])[1], nbytes,
+                               flops=2 * 32 * N * K))
+            del graphs
+        del sws, q4
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default=None)
+    p.add_argument("--dg-tail-only", action="store_true",
+                   help="only the decode GEMM ring-tail vs tail-loop rows")
     p.add_argument("--w4-gemm-only", action="store_true",
                    help="only the gemm_w4 vs F.linear rows")
     p.add_argument("--norm-only", action="store_true",
@@ -117,6 +177,9 @@ def main():
     out = []
     if args.w4_gemm_only:
         w4_gemm_rows(out, dev)
+        return report(out, args)
+    if args.dg_tail_only:
+        dg_tail_rows(out, dev)
         return report(out, args)
 
     # rmsnorm fwd/bwd [2048, 4096]
@@ -367,6 +430,7 @@ def main():
         del q4
 
     w4_gemm_rows(out, dev)
+    dg_tail_rows(out, dev)
 
     # fp8 decode GEMM
     from runbooks_amd.ops.linear import quantize_fp8

@@ -78,7 +78,8 @@ at::Tensor mfma_probe_16x16x32(at::Tensor a, at::Tensor b);
 at::Tensor train_gemm_nt(at::Tensor a, at::Tensor b);
 at::Tensor skinny_gemm(at::Tensor x, at::Tensor w);
 at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N, int64_t K, int64_t force_split,
-                       int64_t layout, int64_t hq, int64_t hkv, int64_t dh, int64_t u);
+                       int64_t layout, int64_t hq, int64_t hkv, int64_t dh, int64_t u,
+                       int64_t tail);
 at::Tensor decode_swizzle_w(at::Tensor w);
 at::Tensor decode_swizzle_x(at::Tensor x);
 int64_t decode_gemm_split(int64_t N, int64_t K);
@@ -86,7 +87,8 @@ bool decode_gemm_supported(int64_t M, int64_t N, int64_t K);
 at::Tensor skinny_gemm_fp8(at::Tensor x, at::Tensor w8, at::Tensor scale);
 std::vector<at::Tensor> w4_swizzle(at::Tensor q, at::Tensor scales);
 at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
-                          int64_t M, int64_t N, int64_t K, int64_t force_split);
+                          int64_t M, int64_t N, int64_t K, int64_t force_split,
+                          int64_t tail);
 int64_t decode_gemm_w4_split(int64_t N, int64_t K);
 bool decode_gemm_w4_supported(int64_t M, int64_t N, int64_t K);
 at::Tensor gemm_w4(at::Tensor x, at::Tensor wq_swz, at::Tensor sc_swz,
@@ -205,7 +207,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("xs"), py::arg("ws"), py::arg("M"), py::arg("N"),
         py::arg("K"), py::arg("force_split") = -1, py::arg("layout") = 0,
         py::arg("hq") = 0, py::arg("hkv") = 0, py::arg("dh") = 0,
-        py::arg("u") = 0);
+        py::arg("u") = 0, py::arg("tail") = -1);
   m.def("decode_swizzle_w", &decode_swizzle_w,
         "one-time [N,K] -> fragment-lane-major weight layout");
   m.def("decode_swizzle_x", &decode_swizzle_x,
@@ -224,7 +226,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "int4 weight-only decode GEMM (group-64 bf16 scales): "
         "y[M<=32,N] = x @ dequant(Wq)^T (bf16)",
         py::arg("xs"), py::arg("wq_swz"), py::arg("sc_swz"), py::arg("M"),
-        py::arg("N"), py::arg("K"), py::arg("force_split") = -1);
+        py::arg("N"), py::arg("K"), py::arg("force_split") = -1,
+        py::arg("tail") = -1);
   m.def("decode_gemm_w4_split", &decode_gemm_w4_split);
   m.def("decode_gemm_w4_supported", &decode_gemm_w4_supported);
   m.def("gemm_w4", &gemm_w4,

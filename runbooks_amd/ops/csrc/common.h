@@ -14,6 +14,10 @@
 
 namespace rb {
 
+// RB_DG_TAIL (decode_gemm.hip, read once): false only for "0", which picks
+// the one-unit-at-a-time K tail of decode_gemm / decode_gemm_w4.
+bool dg_ring_tail();
+
 // ---------------------------------------------------------------------------
 // bf16 <-> f32 (explicit bit ops; avoids header/format portability issues)
 // ---------------------------------------------------------------------------

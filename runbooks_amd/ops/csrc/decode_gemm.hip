@@ -38,6 +38,8 @@
 
 #include <stdlib.h>
 
+#include <algorithm>
+
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 
@@ -127,12 +129,42 @@ __device__ __forceinline__ int epi_col(int nblk, int en, const EpiArgs &e) {
                                                   0, 0, 0);            \
   }
 
+// A tail chunk: the same U loads with the step index clamped to SLAST, the
+// wave's last real step, so the load count stays static (counted vmcnt
+// waits) and nothing outside the wave's own [s0, s1) is read; the repeats
+// re-request one 1 KiB line. Only the first CNT registers are consumed.
+#define RB_LOAD_CHUNK_CLAMP(WB, XB, SBASE, SLAST)                      \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                      \
+    const int sc = min((SBASE) + u, (SLAST));                          \
+    WB[u] = nt_load8v(wseg + (int64_t)sc * 512 + lane8);               \
+    XB[u] = load8v(xs + (int64_t)sc * 512 + lane8);                    \
+  }
+
+// The first CNT (wave-uniform, <= U) k-steps of a chunk, in order. A step
+// that does not exist is branched over, never fed a zero operand: adding
+// +0 could turn a -0 sum into +0.
+#define RB_MFMA_HEAD(WB, XB, CNT)                                      \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                      \
+    if (u < (CNT)) {                                                   \
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(WB[u], XB[u], acc, \
+                                                    0, 0, 0);          \
+    }                                                                  \
+  }
+
 // STORE_BF16: write y bf16 directly (SPLIT == 1). Otherwise store an
 // fp32 slab slice at slabs + kslice*M*N for decode_gemm_combine.
 // U = k-steps (of 16) per unrolled chunk: 8 keeps 3 waves/SIMD, 12
 // trades occupancy (2/SIMD) for a deeper in-flight ring (RB_DG_U=12).
-template <bool STORE_BF16, int U = 8, int EPI = EPI_PLAIN>
-__global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
+// RING_TAIL: the t = (s1 - s0) % 2U steps the ring pairs leave over go
+// through the ring as up to two clamped chunks, all their loads in flight
+// at once (chunk 1 issued under the last B chunk's MFMAs). false keeps
+// the one-step-at-a-time loop (tail = 0 / RB_DG_TAIL=0, for A/B runs and
+// bisecting). Both run the same k-steps in the same order into the same
+// accumulator, so the outputs are bit-identical.
+template <bool STORE_BF16, int U = 8, int EPI = EPI_PLAIN,
+          bool RING_TAIL = true>
+__global__ __launch_bounds__(BLOCK, (RING_TAIL && U == 8) ? 3 : 1) void
+decode_gemm_kernel(
     const uint16_t *__restrict__ xs, const uint16_t *__restrict__ ws,
     uint16_t *__restrict__ yp, float *__restrict__ slabs,
     int M, int N, int K, const EpiArgs ep) {
@@ -152,7 +184,11 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
   const int steps_total = K / 16;
   const int ngroups = split * 4;
   const int spg = (steps_total + ngroups - 1) / ngroups;
-  const int g = kslice * 4 + wid;
+  // The ring tail branches on its step counts and clamps step indices:
+  // tell the compiler the wave index is uniform, so those are scalar
+  // branches and scalar address arithmetic (the old tail keeps its code).
+  const int g = kslice * 4 +
+                (RING_TAIL ? __builtin_amdgcn_readfirstlane(wid) : wid);
   const int s0 = g * spg;
   const int s1 = min(steps_total, s0 + spg);
 
@@ -182,21 +218,63 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_kernel(
   bf16x8v wA[U], xA[U], wB[U], xB[U];
   int s = s0;
   const int nmain = ((s1 - s0) / (2 * U)) * (2 * U);
-  if (nmain > 0) {
-    RB_LOAD_CHUNK(wA, xA, s);
-    const int smain = s0 + nmain;
-    for (; s + 2 * U <= smain; s += 2 * U) {
-      if (s + U < smain) { RB_LOAD_CHUNK(wB, xB, s + U); }
+  if constexpr (RING_TAIL) {
+    const int smain = s0 + max(nmain, 0);
+    const int t1 = min(s1 - smain, U);   // tail chunk 1: 0..U steps
+    const int t2 = s1 - smain - U;       // tail chunk 2: > 0 when it exists
+    const int slast = s1 - 1;
+    if (nmain > 0) {
+      RB_LOAD_CHUNK(wA, xA, s);
+      for (; s + 2 * U < smain; s += 2 * U) {
+        RB_LOAD_CHUNK(wB, xB, s + U);
+        RB_MFMA_CHUNK(wA, xA);
+        RB_LOAD_CHUNK(wA, xA, s + 2 * U);
+        RB_MFMA_CHUNK(wB, xB);
+      }
+      // last pair: the A half it frees takes tail chunk 1, whose loads
+      // fly under the B chunk's MFMAs
+      RB_LOAD_CHUNK(wB, xB, s + U);
       RB_MFMA_CHUNK(wA, xA);
-      if (s + 2 * U < smain) { RB_LOAD_CHUNK(wA, xA, s + 2 * U); }
-      if (s + U < smain) { RB_MFMA_CHUNK(wB, xB); }
+      if (t1 > 0) {
+        RB_LOAD_CHUNK_CLAMP(wA, xA, smain, slast);
+        RB_MFMA_CHUNK(wB, xB);
+        if (t2 > 0) {
+          RB_LOAD_CHUNK_CLAMP(wB, xB, smain + U, slast);
+          RB_MFMA_HEAD(wA, xA, t1);
+          RB_MFMA_HEAD(wB, xB, t2);
+        } else {
+          RB_MFMA_HEAD(wA, xA, t1);
+        }
+      } else {
+        RB_MFMA_CHUNK(wB, xB);
+      }
+    } else if (t1 > 0) {                 // the whole range is tail
+      RB_LOAD_CHUNK_CLAMP(wA, xA, s0, slast);
+      if (t2 > 0) {
+        RB_LOAD_CHUNK_CLAMP(wB, xB, s0 + U, slast);
+        RB_MFMA_HEAD(wA, xA, t1);
+        RB_MFMA_HEAD(wB, xB, t2);
+      } else {
+        RB_MFMA_HEAD(wA, xA, t1);
+      }
     }
-  }
-  // tail: single k-steps, no prefetch (<= 2U-1 iterations)
-  for (; s < s1; ++s) {
-    bf16x8v w1 = nt_load8v(wseg + (int64_t)s * 512 + lane8);
-    bf16x8v x1 = load8v(xs + (int64_t)s * 512 + lane8);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x1, acc, 0, 0, 0);
+  } else {
+    if (nmain > 0) {
+      RB_LOAD_CHUNK(wA, xA, s);
+      const int smain = s0 + nmain;
+      for (; s + 2 * U <= smain; s += 2 * U) {
+        if (s + U < smain) { RB_LOAD_CHUNK(wB, xB, s + U); }
+        RB_MFMA_CHUNK(wA, xA);
+        if (s + 2 * U < smain) { RB_LOAD_CHUNK(wA, xA, s + 2 * U); }
+        if (s + U < smain) { RB_MFMA_CHUNK(wB, xB); }
+      }
+    }
+    // tail: single k-steps, no prefetch (<= 2U-1 iterations)
+    for (; s < s1; ++s) {
+      bf16x8v w1 = nt_load8v(wseg + (int64_t)s * 512 + lane8);
+      bf16x8v x1 = load8v(xs + (int64_t)s * 512 + lane8);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, x1, acc, 0, 0, 0);
+    }
   }
 
   // ---- cross-wave reduction in LDS -------------------------------------
@@ -417,42 +495,84 @@ static int dg_u() {
   return u;
 }
 
+// RB_DG_TAIL=0 (exactly "0"; anything else keeps the default): the
+// one-step-at-a-time K tail (see RING_TAIL) for the raw, glu and rope entry
+// points and for the tail = -1 default of decode_gemm / decode_gemm_w4.
+// Read once.
+bool rb::dg_ring_tail() {
+  static bool t = [] {
+    const char *e = getenv("RB_DG_TAIL");
+    return !(e != nullptr && e[0] == '0' && e[1] == '\0');
+  }();
+  return t;
+}
+
 namespace {
 
-template <bool STORE_BF16, int EPI>
-void launch_dg(int u, int split, hipStream_t stream, const at::Tensor &xs,
-               const at::Tensor &ws, uint16_t *y, float *slabs, int64_t M,
-               int64_t N, int64_t K, const EpiArgs &ep) {
-  const dim3 grid(N / 32, split);
-  if (u == 12)
-    hipLaunchKernelGGL((decode_gemm_kernel<STORE_BF16, 12, EPI>), grid,
+template <bool STORE_BF16, int U, int EPI>
+void launch_dg_u(bool ring_tail, const dim3 &grid, hipStream_t stream,
+                 const at::Tensor &xs, const at::Tensor &ws, uint16_t *y,
+                 float *slabs, int64_t M, int64_t N, int64_t K,
+                 const EpiArgs &ep) {
+  if (ring_tail)
+    hipLaunchKernelGGL((decode_gemm_kernel<STORE_BF16, U, EPI, true>), grid,
                        dim3(BLOCK), 0, stream,
                        (const uint16_t *)xs.data_ptr(),
                        (const uint16_t *)ws.data_ptr(), y, slabs,
                        (int)M, (int)N, (int)K, ep);
   else
-    hipLaunchKernelGGL((decode_gemm_kernel<STORE_BF16, 8, EPI>), grid,
+    hipLaunchKernelGGL((decode_gemm_kernel<STORE_BF16, U, EPI, false>), grid,
                        dim3(BLOCK), 0, stream,
                        (const uint16_t *)xs.data_ptr(),
                        (const uint16_t *)ws.data_ptr(), y, slabs,
                        (int)M, (int)N, (int)K, ep);
 }
 
+// Does any (kslice, wave) group of this launch have a K tail, i.e. a step
+// count that is no multiple of the ring pair 2U? The kernel's partition.
+bool dg_has_tail(int64_t K, int split, int u) {
+  const int steps_total = (int)(K / 16), ngroups = split * 4;
+  const int spg = (steps_total + ngroups - 1) / ngroups;
+  for (int g = 0; g < ngroups; ++g) {
+    const int n = std::min(steps_total, g * spg + spg) - g * spg;
+    if (n > 0 && n % (2 * u) != 0) return true;
+  }
+  return false;
+}
+
+// The ring-tail instantiation is launched only where some wave has a tail:
+// a launch without one (qkv, gate-up, o_proj, lm_head at U = 8) keeps the
+// kernel, and so the main-loop schedule, it had before the ring tail.
+template <bool STORE_BF16, int EPI>
+void launch_dg(int u, bool ring_tail, int split, hipStream_t stream,
+               const at::Tensor &xs, const at::Tensor &ws, uint16_t *y,
+               float *slabs, int64_t M, int64_t N, int64_t K,
+               const EpiArgs &ep) {
+  const dim3 grid(N / 32, split);
+  ring_tail = ring_tail && dg_has_tail(K, split, u == 12 ? 12 : 8);
+  if (u == 12)
+    launch_dg_u<STORE_BF16, 12, EPI>(ring_tail, grid, stream, xs, ws, y,
+                                     slabs, M, N, K, ep);
+  else
+    launch_dg_u<STORE_BF16, 8, EPI>(ring_tail, grid, stream, xs, ws, y,
+                                    slabs, M, N, K, ep);
+}
+
 // un-permuting (or plain) store, by layout tag
 template <bool STORE_BF16>
-void launch_dg_store(int64_t layout, int u, int split, hipStream_t stream,
-                     const at::Tensor &xs, const at::Tensor &ws, uint16_t *y,
-                     float *slabs, int64_t M, int64_t N, int64_t K,
-                     const EpiArgs &ep) {
+void launch_dg_store(int64_t layout, int u, bool ring_tail, int split,
+                     hipStream_t stream, const at::Tensor &xs,
+                     const at::Tensor &ws, uint16_t *y, float *slabs,
+                     int64_t M, int64_t N, int64_t K, const EpiArgs &ep) {
   if (layout == LAYOUT_GLU16)
-    launch_dg<STORE_BF16, EPI_GLU_STORE>(u, split, stream, xs, ws, y, slabs,
-                                         M, N, K, ep);
+    launch_dg<STORE_BF16, EPI_GLU_STORE>(u, ring_tail, split, stream, xs, ws,
+                                         y, slabs, M, N, K, ep);
   else if (layout == LAYOUT_ROPE16)
-    launch_dg<STORE_BF16, EPI_ROPE_STORE>(u, split, stream, xs, ws, y, slabs,
-                                          M, N, K, ep);
+    launch_dg<STORE_BF16, EPI_ROPE_STORE>(u, ring_tail, split, stream, xs, ws,
+                                          y, slabs, M, N, K, ep);
   else
-    launch_dg<STORE_BF16, EPI_PLAIN>(u, split, stream, xs, ws, y, slabs,
-                                     M, N, K, ep);
+    launch_dg<STORE_BF16, EPI_PLAIN>(u, ring_tail, split, stream, xs, ws, y,
+                                     slabs, M, N, K, ep);
 }
 
 EpiArgs layout_args(int64_t layout, int64_t N, int64_t hq, int64_t hkv,
@@ -521,13 +641,14 @@ at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M,
   const int split = (int)decode_gemm_split(N, K);
   if (split == 1) {
     auto y = at::empty({M, N}, xs.options());
-    launch_dg_store<true>(layout, dg_u(), 1, stream, xs, ws,
+    launch_dg_store<true>(layout, dg_u(), rb::dg_ring_tail(), 1, stream, xs, ws,
                           (uint16_t *)y.data_ptr(), nullptr, M, N, K, ep);
     return y;
   }
   auto slabs = at::empty({split, M, N}, xs.options().dtype(at::kFloat));
-  launch_dg_store<false>(layout, dg_u(), split, stream, xs, ws, nullptr,
-                         (float *)slabs.data_ptr(), M, N, K, ep);
+  launch_dg_store<false>(layout, dg_u(), rb::dg_ring_tail(), split, stream,
+                         xs, ws, nullptr, (float *)slabs.data_ptr(), M, N, K,
+                         ep);
   return slabs;
 }
 
@@ -535,10 +656,13 @@ at::Tensor decode_gemm_raw(at::Tensor xs, at::Tensor ws, int64_t M,
 // the ORIGINAL y[M,N] = x[M,K] @ W[N,K]^T problem. y is row-major in the
 // original column order whatever the weight layout.
 // u picks the k-steps per ring half: 0 = the default 8, 12 = the deeper
-// ring that RB_DG_U=12 gives the raw/fused entry points.
+// ring that RB_DG_U=12 gives the raw/fused entry points. tail picks the K
+// tail: 0 = the one-step loop, > 0 = through the ring, < 0 (default) =
+// what RB_DG_TAIL says (the ring unless it is 0).
 at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
                        int64_t K, int64_t force_split, int64_t layout,
-                       int64_t hq, int64_t hkv, int64_t dh, int64_t u) {
+                       int64_t hq, int64_t hkv, int64_t dh, int64_t u,
+                       int64_t tail) {
   TORCH_CHECK(xs.is_cuda() && ws.is_cuda() && xs.is_contiguous() &&
               ws.is_contiguous(), "decode_gemm: contiguous GPU tensors");
   TORCH_CHECK(xs.scalar_type() == at::kBFloat16 &&
@@ -551,6 +675,7 @@ at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
   TORCH_CHECK(u == 0 || u == 12, "decode_gemm: u must be 0 (8) or 12, got ",
               u);
   const int ring = u == 12 ? 12 : 8;
+  const bool ring_tail = tail < 0 ? rb::dg_ring_tail() : tail != 0;
   const EpiArgs ep = layout_args(layout, N, hq, hkv, dh);
 
   auto stream = at::cuda::getCurrentHIPStream();
@@ -558,12 +683,12 @@ at::Tensor decode_gemm(at::Tensor xs, at::Tensor ws, int64_t M, int64_t N,
   const int split = force_split > 0 ? (int)force_split
                                     : (int)decode_gemm_split(N, K);
   if (split == 1) {
-    launch_dg_store<true>(layout, ring, 1, stream, xs, ws,
+    launch_dg_store<true>(layout, ring, ring_tail, 1, stream, xs, ws,
                           (uint16_t *)y.data_ptr(), nullptr, M, N, K, ep);
   } else {
     auto slabs = at::empty({split, M, N}, xs.options().dtype(at::kFloat));
-    launch_dg_store<false>(layout, ring, split, stream, xs, ws, nullptr,
-                           (float *)slabs.data_ptr(), M, N, K, ep);
+    launch_dg_store<false>(layout, ring, ring_tail, split, stream, xs, ws,
+                           nullptr, (float *)slabs.data_ptr(), M, N, K, ep);
     const int64_t mn = M * N;
     const int grid = rb::rb_grid_1d(mn / 4, 256);
     hipLaunchKernelGGL(decode_gemm_combine_kernel, dim3(grid), dim3(256),
@@ -588,11 +713,11 @@ at::Tensor decode_gemm_glu(at::Tensor xs, at::Tensor ws, int64_t M,
   ep.swz = (uint16_t *)swz.data_ptr();
   auto stream = at::cuda::getCurrentHIPStream();
   if (gelu)
-    launch_dg<true, EPI_GEGLU>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
-                               M, N, K, ep);
+    launch_dg<true, EPI_GEGLU>(dg_u(), rb::dg_ring_tail(), 1, stream, xs, ws,
+                               nullptr, nullptr, M, N, K, ep);
   else
-    launch_dg<true, EPI_SWIGLU>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
-                                M, N, K, ep);
+    launch_dg<true, EPI_SWIGLU>(dg_u(), rb::dg_ring_tail(), 1, stream, xs, ws,
+                                nullptr, nullptr, M, N, K, ep);
   return swz;
 }
 
@@ -642,10 +767,10 @@ at::Tensor decode_gemm_rope_append(at::Tensor xs, at::Tensor ws, int64_t M,
   const bool vt = v_cache.size(2) == dh && v_cache.size(3) == bs && dh != bs;
   auto stream = at::cuda::getCurrentHIPStream();
   if (vt)
-    launch_dg<true, EPI_ROPE_VT>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
-                                 M, N, K, ep);
+    launch_dg<true, EPI_ROPE_VT>(dg_u(), rb::dg_ring_tail(), 1, stream, xs, ws,
+                                 nullptr, nullptr, M, N, K, ep);
   else
-    launch_dg<true, EPI_ROPE>(dg_u(), 1, stream, xs, ws, nullptr, nullptr,
-                              M, N, K, ep);
+    launch_dg<true, EPI_ROPE>(dg_u(), rb::dg_ring_tail(), 1, stream, xs, ws,
+                              nullptr, nullptr, M, N, K, ep);
   return q;
 }

@@ -40,10 +40,13 @@
 // Fragment maps: see decode_gemm.hip (A = W, so C cols = m).
 //
 // Resource usage (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage):
-//   decode_gemm_w4_kernel<true> and <false>: 202 VGPRs + 16 AGPRs, private
-//   segment (scratch) 0, 16 KiB LDS, occupancy 2 waves/SIMD (the launch
-//   bound asks for 1 WG = 1 wave/SIMD; the ring, not occupancy, keeps
-//   the bytes in flight).
+//   decode_gemm_w4_kernel<*, true> (ring tail): 165 VGPRs, accumulator
+//   included, no AGPRs, private segment (scratch) 0, 16 KiB LDS, 3
+//   waves/SIMD; <*, false> (one-group tail loop): 202 VGPRs + 16 AGPRs,
+//   scratch 0, 2 waves/SIMD. The grid puts at most a few waves on a SIMD;
+//   the ring, not occupancy, keeps the bytes in flight.
+
+#include <algorithm>
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -94,10 +97,45 @@ using rb::w4_dequant8;
     }                                                                    \
   }
 
+// A tail chunk: the same U group loads with the group index clamped to
+// GLAST, the wave's last real group, so the load count stays static
+// (counted vmcnt waits) and nothing outside the wave's own [g0, g1) is
+// read. Only the first CNT groups are consumed.
+#define RB_W4_LOAD_CLAMP(WB, SB, XB, GBASE, GLAST)                       \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                        \
+    const int gc = min((GBASE) + u, (GLAST));                            \
+    WB[u] = __builtin_nontemporal_load(reinterpret_cast<const u32x4v *>( \
+        wseg + (int64_t)gc * 1024 + lane * 16));                         \
+    SB[u] = sseg[(int64_t)gc * 32 + col];                                \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                      \
+      XB[u * 4 + j] = load8v(xs + ((int64_t)gc * 4 + j) * 512 + lane8);  \
+    }                                                                    \
+  }
+
+// The first CNT (wave-uniform, <= U) groups of a chunk, in order. A group
+// that does not exist is branched over, never fed a zero operand.
+#define RB_W4_MFMA_HEAD(WB, SB, XB, CNT)                                 \
+  _Pragma("unroll") for (int u = 0; u < U; ++u) {                        \
+    if (u < (CNT)) {                                                     \
+      const float s = rb::bf16_to_f32(SB[u]);                            \
+      const float nb = -136.0f * s;                                      \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) {                    \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                   \
+            w4_dequant8(WB[u][j], s, nb), XB[u * 4 + j], acc, 0, 0, 0);  \
+      }                                                                  \
+    }                                                                    \
+  }
+
 // STORE_BF16: write y bf16 directly (split == 1). Otherwise store an fp32
 // slab slice at slabs + kslice*M*N for the combine kernel.
-template <bool STORE_BF16>
-__global__ __launch_bounds__(BLOCK, 1) void decode_gemm_w4_kernel(
+// RING_TAIL: as in decode_gemm.hip, over groups: the (g1 - g0) % 2U groups
+// the ring pairs leave over go through the ring as up to two clamped
+// chunks with all their loads in flight at once; false keeps the
+// one-group-at-a-time loop (tail = 0 / RB_DG_TAIL=0). Same groups, same
+// order, same accumulator: bit-identical outputs.
+template <bool STORE_BF16, bool RING_TAIL>
+__global__ __launch_bounds__(BLOCK, RING_TAIL ? 2 : 1) void
+decode_gemm_w4_kernel(
     const uint16_t *__restrict__ xs, const uint8_t *__restrict__ wq,
     const uint16_t *__restrict__ sc, uint16_t *__restrict__ yp,
     float *__restrict__ slabs, int M, int N, int K) {
@@ -119,7 +157,9 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_w4_kernel(
   const int groups_total = K / 64;
   const int nranges = split * 4;
   const int gpr = (groups_total + nranges - 1) / nranges;
-  const int g0 = min(groups_total, (kslice * 4 + wid) * gpr);
+  // uniform wave index for the ring tail's scalar branches and clamps
+  const int wu = RING_TAIL ? __builtin_amdgcn_readfirstlane(wid) : wid;
+  const int g0 = min(groups_total, (kslice * 4 + wu) * gpr);
   const int g1 = min(groups_total, g0 + gpr);
 
   const uint8_t *wseg = wq + (int64_t)nblk * groups_total * 1024;
@@ -132,28 +172,70 @@ __global__ __launch_bounds__(BLOCK, 1) void decode_gemm_w4_kernel(
   bf16x8v xA[4 * U], xB[4 * U];
   int g = g0;
   const int nmain = ((g1 - g0) / (2 * U)) * (2 * U);
-  if (nmain > 0) {
-    RB_W4_LOAD(wA, sA, xA, g);
+  if constexpr (RING_TAIL) {
     const int gmain = g0 + nmain;
-    for (; g + 2 * U <= gmain; g += 2 * U) {
+    const int t1 = min(g1 - gmain, U);   // tail chunk 1: 0..U groups
+    const int t2 = g1 - gmain - U;       // tail chunk 2: > 0 when it exists
+    const int glast = g1 - 1;
+    if (nmain > 0) {
+      RB_W4_LOAD(wA, sA, xA, g);
+      for (; g + 2 * U < gmain; g += 2 * U) {
+        RB_W4_LOAD(wB, sB, xB, g + U);
+        RB_W4_MFMA(wA, sA, xA);
+        RB_W4_LOAD(wA, sA, xA, g + 2 * U);
+        RB_W4_MFMA(wB, sB, xB);
+      }
+      // last pair: the A half it frees takes tail chunk 1, whose loads
+      // fly under the B chunk's MFMAs
       RB_W4_LOAD(wB, sB, xB, g + U);
       RB_W4_MFMA(wA, sA, xA);
-      if (g + 2 * U < gmain) { RB_W4_LOAD(wA, sA, xA, g + 2 * U); }
-      RB_W4_MFMA(wB, sB, xB);
+      if (t1 > 0) {
+        RB_W4_LOAD_CLAMP(wA, sA, xA, gmain, glast);
+        RB_W4_MFMA(wB, sB, xB);
+        if (t2 > 0) {
+          RB_W4_LOAD_CLAMP(wB, sB, xB, gmain + U, glast);
+          RB_W4_MFMA_HEAD(wA, sA, xA, t1);
+          RB_W4_MFMA_HEAD(wB, sB, xB, t2);
+        } else {
+          RB_W4_MFMA_HEAD(wA, sA, xA, t1);
+        }
+      } else {
+        RB_W4_MFMA(wB, sB, xB);
+      }
+    } else if (t1 > 0) {                 // the whole range is tail
+      RB_W4_LOAD_CLAMP(wA, sA, xA, g0, glast);
+      if (t2 > 0) {
+        RB_W4_LOAD_CLAMP(wB, sB, xB, g0 + U, glast);
+        RB_W4_MFMA_HEAD(wA, sA, xA, t1);
+        RB_W4_MFMA_HEAD(wB, sB, xB, t2);
+      } else {
+        RB_W4_MFMA_HEAD(wA, sA, xA, t1);
+      }
     }
-  }
-  // tail: single groups, no prefetch (<= 2U-1 iterations)
-  for (; g < g1; ++g) {
-    const u32x4v w1 = __builtin_nontemporal_load(
-        reinterpret_cast<const u32x4v *>(wseg + (int64_t)g * 1024 +
-                                         lane * 16));
-    const float s = rb::bf16_to_f32(sseg[(int64_t)g * 32 + col]);
-    const float nb = -136.0f * s;
+  } else {
+    if (nmain > 0) {
+      RB_W4_LOAD(wA, sA, xA, g);
+      const int gmain = g0 + nmain;
+      for (; g + 2 * U <= gmain; g += 2 * U) {
+        RB_W4_LOAD(wB, sB, xB, g + U);
+        RB_W4_MFMA(wA, sA, xA);
+        if (g + 2 * U < gmain) { RB_W4_LOAD(wA, sA, xA, g + 2 * U); }
+        RB_W4_MFMA(wB, sB, xB);
+      }
+    }
+    // tail: single groups, no prefetch (<= 2U-1 iterations)
+    for (; g < g1; ++g) {
+      const u32x4v w1 = __builtin_nontemporal_load(
+          reinterpret_cast<const u32x4v *>(wseg + (int64_t)g * 1024 +
+                                           lane * 16));
+      const float s = rb::bf16_to_f32(sseg[(int64_t)g * 32 + col]);
+      const float nb = -136.0f * s;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const bf16x8v x1 = load8v(xs + ((int64_t)g * 4 + j) * 512 + lane8);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-          w4_dequant8(w1[j], s, nb), x1, acc, 0, 0, 0);
+      for (int j = 0; j < 4; ++j) {
+        const bf16x8v x1 = load8v(xs + ((int64_t)g * 4 + j) * 512 + lane8);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            w4_dequant8(w1[j], s, nb), x1, acc, 0, 0, 0);
+      }
     }
   }
 
@@ -209,6 +291,42 @@ __global__ void decode_gemm_w4_combine_kernel(
   }
 }
 
+// Does any (kslice, wave) range of this launch have a K tail, i.e. a group
+// count that is no multiple of the ring pair 2U? The kernel's partition.
+bool w4_has_tail(int64_t K, int split) {
+  const int groups_total = (int)(K / 64), nranges = split * 4;
+  const int gpr = (groups_total + nranges - 1) / nranges;
+  for (int r = 0; r < nranges; ++r) {
+    const int g0 = std::min(groups_total, r * gpr);
+    const int n = std::min(groups_total, g0 + gpr) - g0;
+    if (n % (2 * U) != 0) return true;
+  }
+  return false;
+}
+
+// The ring-tail instantiation is launched only where some wave has a tail;
+// a launch without one keeps the kernel it had before the ring tail.
+template <bool STORE_BF16>
+void launch_w4(bool ring_tail, const dim3 &grid, hipStream_t stream,
+               const at::Tensor &xs, const at::Tensor &wq_swz,
+               const at::Tensor &sc_swz, uint16_t *y, float *slabs,
+               int64_t M, int64_t N, int64_t K) {
+  if (ring_tail && w4_has_tail(K, (int)grid.y))
+    hipLaunchKernelGGL((decode_gemm_w4_kernel<STORE_BF16, true>), grid,
+                       dim3(BLOCK), 0, stream,
+                       (const uint16_t *)xs.data_ptr(),
+                       (const uint8_t *)wq_swz.data_ptr(),
+                       (const uint16_t *)sc_swz.data_ptr(), y, slabs,
+                       (int)M, (int)N, (int)K);
+  else
+    hipLaunchKernelGGL((decode_gemm_w4_kernel<STORE_BF16, false>), grid,
+                       dim3(BLOCK), 0, stream,
+                       (const uint16_t *)xs.data_ptr(),
+                       (const uint8_t *)wq_swz.data_ptr(),
+                       (const uint16_t *)sc_swz.data_ptr(), y, slabs,
+                       (int)M, (int)N, (int)K);
+}
+
 }  // namespace
 
 // Cross-WG k-split, same load-balance reasoning as decode_gemm_split:
@@ -254,9 +372,11 @@ std::vector<at::Tensor> w4_swizzle(at::Tensor q, at::Tensor scales) {
 // w4_swizzle; M/N/K of the ORIGINAL y[M,N] = x[M,K] @ W[N,K]^T problem.
 // Workspaces (y, slabs) come from the caching allocator like
 // decode_gemm's, so they are pointer-stable under hipGraph capture.
+// tail: 0 = the one-group loop, > 0 = through the ring, < 0 (default) =
+// what RB_DG_TAIL says (the ring unless it is 0).
 at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
                           int64_t M, int64_t N, int64_t K,
-                          int64_t force_split) {
+                          int64_t force_split, int64_t tail) {
   TORCH_CHECK(xs.is_cuda() && wq_swz.is_cuda() && sc_swz.is_cuda() &&
               xs.is_contiguous() && wq_swz.is_contiguous() &&
               sc_swz.is_contiguous(),
@@ -271,27 +391,19 @@ at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
   TORCH_CHECK(wq_swz.numel() == N * K / 2, "decode_gemm_w4: wq_swz size");
   TORCH_CHECK(sc_swz.numel() == N * (K / 64), "decode_gemm_w4: sc_swz size");
   TORCH_CHECK(force_split <= 8, "decode_gemm_w4: force_split <= 8");
+  const bool ring_tail = tail < 0 ? rb::dg_ring_tail() : tail != 0;
 
   auto stream = at::cuda::getCurrentHIPStream();
   auto y = at::empty({M, N}, xs.options());
   const int split = force_split > 0 ? (int)force_split
                                     : (int)decode_gemm_w4_split(N, K);
   if (split == 1) {
-    hipLaunchKernelGGL((decode_gemm_w4_kernel<true>), dim3(N / 32, 1),
-                       dim3(BLOCK), 0, stream,
-                       (const uint16_t *)xs.data_ptr(),
-                       (const uint8_t *)wq_swz.data_ptr(),
-                       (const uint16_t *)sc_swz.data_ptr(),
-                       (uint16_t *)y.data_ptr(), nullptr,
-                       (int)M, (int)N, (int)K);
+    launch_w4<true>(ring_tail, dim3(N / 32, 1), stream, xs, wq_swz, sc_swz,
+                    (uint16_t *)y.data_ptr(), nullptr, M, N, K);
   } else {
     auto slabs = at::empty({split, M, N}, xs.options().dtype(at::kFloat));
-    hipLaunchKernelGGL((decode_gemm_w4_kernel<false>), dim3(N / 32, split),
-                       dim3(BLOCK), 0, stream,
-                       (const uint16_t *)xs.data_ptr(),
-                       (const uint8_t *)wq_swz.data_ptr(),
-                       (const uint16_t *)sc_swz.data_ptr(), nullptr,
-                       (float *)slabs.data_ptr(), (int)M, (int)N, (int)K);
+    launch_w4<false>(ring_tail, dim3(N / 32, split), stream, xs, wq_swz,
+                     sc_swz, nullptr, (float *)slabs.data_ptr(), M, N, K);
     const int64_t mn = M * N;
     const int grid = rb::rb_grid_1d(mn / 4, 256);
     hipLaunchKernelGGL(decode_gemm_w4_combine_kernel, dim3(grid), dim3(256),
