@@ -161,6 +161,56 @@ def dg_tail_rows(out, dev="cuda"):
         del sws, q4
 
 
+def mt_rows(out, dev="cuda"):
+    """csrc/decode_gemm_mt.hip (bf16 weight stream, 32 < M <= 256) at the
+    llama2-7b projection shapes against F.linear on the [N,K] master
+    (hipBLASLt, the route these row counts take without RB_DECODE_GEMM_MT).
+    The timed call is the whole route: operand swizzle + GEMM (+ combine at
+    split > 1) from a row-major x. As in dg_tail_rows, each variant is a
+    graph of 20 calls over ten rotating weights (>= 335 MB, past the
+    Infinity Cache) and the replays are timed alternately, five rounds; the
+    row carries the median round, `min_us` / `max_us` over the rounds and
+    the same for F.linear. `win`: the slowest mt round beats the fastest
+    F.linear round."""
+    bf16 = torch.bfloat16
+    e = ops.ext()
+    for name, N, K in (("qkv", 12288, 4096), ("o_proj", 4096, 4096),
+                       ("gate_up", 22016, 4096), ("down", 4096, 11008),
+                       ("lm_head", 32000, 4096)):
+        ws = [torch.randn(N, K, dtype=bf16, device=dev) * 0.02
+              for _ in range(10)]
+        sws = [e.decode_swizzle_w(w) for w in ws]
+        for M in (40, 64, 160, 256):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            calls = {
+                "mt": lambda j: e.decode_gemm_mt(x, sws[j % 10], N, K),
+                "lin": lambda j: torch.nn.functional.linear(x, ws[j % 10])}
+            graphs = {}
+            for k, call in calls.items():
+                call(0)
+                torch.cuda.synchronize()
+                graphs[k] = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graphs[k]):
+                    for j in range(20):
+                        call(j)
+            us = {k: [] for k in calls}
+            for _ in range(5):
+                for k in calls:
+                    us[k].append(timeit(graphs[k].replay, iters=20,
+                                        warmup=5) / 20)
+            mt, lin = sorted(us["mt"]), sorted(us["lin"])
+            r = row(f"decode_gemm_mt {name}", f"{M}x{N}x{K}", mt[2],
+                    N * K * 2, flops=2 * M * N * K)
+            r.update(min_us=round(mt[0], 2), max_us=round(mt[-1], 2),
+                     f_linear_bf16_us=round(lin[2], 2),
+                     f_linear_min_us=round(lin[0], 2),
+                     f_linear_max_us=round(lin[-1], 2),
+                     ratio=round(mt[2] / lin[2], 2), win=mt[-1] < lin[0])
+            out.append(r)
+            del graphs
+        del ws, sws
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default=None)
@@ -168,6 +218,8 @@ def main():
                    help="only the decode GEMM ring-tail vs tail-loop rows")
     p.add_argument("--w4-gemm-only", action="store_true",
                    help="only the gemm_w4 vs F.linear rows")
+    p.add_argument("--mt-only", action="store_true",
+                   help="only the decode_gemm_mt vs F.linear rows")
     p.add_argument("--norm-only", action="store_true",
                    help="stop after the rmsnorm rows")
     args = p.parse_args()
@@ -180,6 +232,9 @@ def main():
         return report(out, args)
     if args.dg_tail_only:
         dg_tail_rows(out, dev)
+        return report(out, args)
+    if args.mt_only:
+        mt_rows(out, dev)
         return report(out, args)
 
     # rmsnorm fwd/bwd [2048, 4096]
@@ -431,6 +486,7 @@ def main():
 
     w4_gemm_rows(out, dev)
     dg_tail_rows(out, dev)
+    mt_rows(out, dev)
 
     # fp8 decode GEMM
     from runbooks_amd.ops.linear import quantize_fp8

@@ -8,7 +8,10 @@
   step    llama2-7b shapes (random weights), hipGraph replays: the verify
           step at T = 5 against the decode step at B 1/8/32, context 512.
           r = verify / decode; a verify step pays for itself once it
-          accepts r - 1 drafts on average.
+          accepts r - 1 drafts on average. With --mt a second verify graph
+          is captured under RB_DECODE_GEMM_MT=1 (its 5B-row GEMMs on
+          decode_gemm_mt.hip, not hipBLASLt) and timed in the same rounds
+          as "verify_T5_mt" (ratio_mt); --step-only skips the other parts.
   engine  tokens/s of Engine(speculative=4) against Engine(batch_sampler=
           True) at B = 8, 64 new tokens: a prompt that repeats itself with
           the n-gram drafter, the same with a drafter replaying the
@@ -19,8 +22,10 @@ Times are device events around back-to-back launches / replays, rounds of
 the variants interleaved in one process; median and min over the rounds.
 
     python benchmarks/spec_decode.py [OUT.json] [--kernel-only]
+                                     [--mt] [--step-only]
 """
 import json
+import os
 import statistics
 import sys
 import time
@@ -38,6 +43,8 @@ DEV = "cuda:0"
 BS = ops.BLOCK_SIZE
 T = 5
 kernel_only = "--kernel-only" in sys.argv
+step_only = "--step-only" in sys.argv
+with_mt = "--mt" in sys.argv
 _pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 out_path = _pos[0] if _pos else "spec_decode.json"
 
@@ -127,14 +134,29 @@ def bench_step(model):
         ver = ([[7] * T] * B, [pos] * B,
                [[r[p // BS] * BS + p % BS for p in pos] for r in rows], rows,
                [ctx + T] * B)
-        r = rounds({"decode": lambda: gd.decode(*dec),
-                    "verify_T5": lambda: gd.verify(*ver)}, 20)
+        variants = {"decode": lambda: gd.decode(*dec),
+                    "verify_T5": lambda: gd.verify(*ver)}
+        gd_mt = None
+        if with_mt and B * T > 32:
+            # the switch is read when the graph is captured, at the first
+            # verify call; the decode step and the graph above never see it
+            gd.verify(*ver)
+            gd_mt = GraphedDecoder(model, caches, B, per_seq, nblocks - 1, DEV)
+            gd_mt.enable_verify(T)
+            os.environ["RB_DECODE_GEMM_MT"] = "1"
+            gd_mt.verify(*ver)
+            del os.environ["RB_DECODE_GEMM_MT"]
+            variants["verify_T5_mt"] = lambda: gd_mt.verify(*ver)
+        r = rounds(variants, 20)
         ratio = r["verify_T5"]["median_us"] / r["decode"]["median_us"]
         r["ratio"] = round(ratio, 3)
+        if gd_mt is not None:
+            r["ratio_mt"] = round(r["verify_T5_mt"]["median_us"] /
+                                  r["decode"]["median_us"], 3)
         r["break_even_accepted_per_step"] = round(ratio - 1, 3)
         res[f"B{B}"] = r
         print(f"step B={B}", r, flush=True)
-        del gd, caches
+        del gd, gd_mt, caches
     return res
 
 
@@ -193,14 +215,15 @@ def bench_engine():
 
 
 def main():
-    res = {"kernel": bench_kernel()}
+    res = {} if step_only else {"kernel": bench_kernel()}
     if not kernel_only:
         model = fuse_for_inference(build_model(
             "llama2-7b", dtype=torch.bfloat16, device=DEV).eval())
         res["step"] = bench_step(model)
         del model
         torch.cuda.empty_cache()
-        res["engine"] = bench_engine()
+        if not step_only:
+            res["engine"] = bench_engine()
     with open(out_path, "w") as f:
         json.dump(res, f, indent=1)
 

@@ -13,7 +13,8 @@ from .attention import (causal_attention, flash_prefill, paged_decode,  # noqa: 
                         paged_prefill_batch_ref, paged_prefill_plan,
                         paged_prefill_ref, paged_verify, paged_verify_ref)
 from .kvcache import BLOCK_SIZE, alloc_kv_cache, kv_append, kv_append_ref  # noqa: F401
-from .linear import (Linear, decode_layout, decode_linear_glu,  # noqa: F401
+from .linear import (Linear, decode_gemm_mt, decode_gemm_mt_enabled,  # noqa: F401
+                     decode_layout, decode_linear_glu,
                      decode_linear_raw, decode_linear_rope_append,
                      fast_linear, fused_epilogue_ok, w4_prefill_enabled)
 from .lora_serve import (lora_expand_, lora_expand_ref_, lora_shrink,  # noqa: F401

@@ -84,6 +84,10 @@ at::Tensor decode_swizzle_w(at::Tensor w);
 at::Tensor decode_swizzle_x(at::Tensor x);
 int64_t decode_gemm_split(int64_t N, int64_t K);
 bool decode_gemm_supported(int64_t M, int64_t N, int64_t K);
+at::Tensor decode_gemm_mt(at::Tensor x, at::Tensor ws, int64_t n, int64_t k, int64_t layout,
+                          int64_t hq, int64_t hkv, int64_t dh, int64_t force_split);
+at::Tensor decode_swizzle_x_mt(at::Tensor x);
+bool decode_gemm_mt_supported(int64_t M, int64_t N, int64_t K);
 at::Tensor skinny_gemm_fp8(at::Tensor x, at::Tensor w8, at::Tensor scale);
 std::vector<at::Tensor> w4_swizzle(at::Tensor q, at::Tensor scales);
 at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
@@ -214,6 +218,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-call x -> B-fragment lane order (zero-padded to M=32)");
   m.def("decode_gemm_split", &decode_gemm_split);
   m.def("decode_gemm_supported", &decode_gemm_supported);
+  m.def("decode_gemm_mt", &decode_gemm_mt,
+        "m-tiled weight-stream GEMM over the decode weight copy: "
+        "y[32<M<=256,N] = x @ W^T (bf16), x row-major",
+        py::arg("x"), py::arg("ws"), py::arg("n"), py::arg("k"),
+        py::arg("layout") = 0, py::arg("hq") = 0, py::arg("hkv") = 0,
+        py::arg("dh") = 0, py::arg("force_split") = -1);
+  m.def("decode_swizzle_x_mt", &decode_swizzle_x_mt,
+        "x [M<=256,K] -> [K/16][ceil(M/32)][lane][8] B-fragment tiles "
+        "(rows >= M zero)");
+  m.def("decode_gemm_mt_supported", &decode_gemm_mt_supported);
   m.def("mfma_probe_16x16x32", &mfma_probe_16x16x32,
         "layout probe: one 16x16x32 bf16 MFMA as a plain matmul");
   m.def("train_gemm_nt", &train_gemm_nt,

@@ -18,6 +18,11 @@ namespace rb {
 // the one-unit-at-a-time K tail of decode_gemm / decode_gemm_w4.
 bool dg_ring_tail();
 
+// decode_gemm.hip's split-K combine, slabs [split, mn] f32 -> y [mn] bf16
+// (mn % 4 == 0), for the other kernels that write such slabs.
+void dg_combine(const float *slabs, uint16_t *y, int split, int64_t mn,
+                hipStream_t stream);
+
 // ---------------------------------------------------------------------------
 // bf16 <-> f32 (explicit bit ops; avoids header/format portability issues)
 // ---------------------------------------------------------------------------

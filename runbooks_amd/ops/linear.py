@@ -138,6 +138,43 @@ def w4_prefill_enabled() -> bool:
     return bool(_W4_RELEASED)
 
 
+def decode_gemm_mt_enabled() -> bool:
+    """RB_DECODE_GEMM_MT=1 sends bf16 GEMMs of 33..DECODE_GEMM_MT_MAX_M
+    rows on a weight with a
+    registered decode copy (speculative verify, decode at B > 32, short
+    prompt chunks) to csrc/decode_gemm_mt.hip instead of F.linear on the
+    master. Off by default; read at every call."""
+    return os.environ.get("RB_DECODE_GEMM_MT", "0") == "1"
+
+
+# Largest row count fast_linear routes to decode_gemm_mt. The kernel entry
+# point serves up to 256 rows, but at 256 it lost to hipBLASLt on all five
+# llama2-7b shapes (1.29-2.19x its time) while 160 rows still had wins
+# (down-proj 0.68x, o_proj 0.95x): profiles/README.md, "decode_gemm_mt".
+DECODE_GEMM_MT_MAX_M = 160
+
+
+def _decode_gemm_mt(x, dw, m, n, k):
+    tag, hq, hkv, dh = dw[2]
+    y = _backend.ext().decode_gemm_mt(x.reshape(m, k).contiguous(), dw[0],
+                                      n, k, _LAYOUT_ID[tag], hq, hkv, dh)
+    return y.view(*x.shape[:-1], n)
+
+
+def decode_gemm_mt(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """x [..., K] bf16 (33..256 rows) @ weight^T through
+    csrc/decode_gemm_mt.hip on `weight`'s registered decode copy, whatever
+    its layout tag; y comes back in the original column order. Row r is
+    bit-identical to the decode GEMM's result for that row. Raises when the
+    weight has no registered decode copy or the shape is unsupported."""
+    dw = _registry_get(_DECODE_W_REGISTRY, weight)
+    if dw is None:
+        raise RuntimeError("decode_gemm_mt: weight has no registered decode "
+                           "copy (register_decode_weight)")
+    n, k = dw[1]
+    return _decode_gemm_mt(x, dw, x.numel() // k, n, k)
+
+
 def _released_get(weight: torch.Tensor):
     entry = _W4_RELEASED.get(id(weight))
     if entry is None or entry[-1]() is not weight:
@@ -327,12 +364,22 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                 y = _backend.ext().skinny_gemm(x.reshape(m, k).contiguous(),
                                                weight)
                 return y.view(*x.shape[:-1], n)
-        elif (_W4_REGISTRY or released) and w4_prefill_enabled():
+        elif (_W4_REGISTRY or released) and w4_prefill_enabled() and \
+                (q4 := _w4_get(weight)) is not None:
             # int4 weight-only GEMM at large M: prefill, chunked and
             # batched prefill multiply by the weights decode streams
-            q4 = _w4_get(weight)
-            if q4 is not None and _backend.ext().gemm_w4_supported(m, n, k):
+            if _backend.ext().gemm_w4_supported(m, n, k):
                 return gemm_w4(x, q4)
+        elif m <= DECODE_GEMM_MT_MAX_M and _USE_DECODE_GEMM and \
+                not released and decode_gemm_mt_enabled():
+            # 33..256 rows are still a weight stream: same decode copy, one
+            # W fragment feeding ceil(m/32) m-tiles. A weight that also has
+            # an fp8 or int4 registration keeps its route (F.linear here).
+            dw = _registry_get(_DECODE_W_REGISTRY, weight)
+            if dw is not None and _w4_get(weight) is None and \
+                    _registry_get(_FP8_REGISTRY, weight) is None and \
+                    _backend.ext().decode_gemm_mt_supported(m, n, k):
+                return _decode_gemm_mt(x, dw, m, n, k)
     if released:
         _check_master(weight, "the F.linear path (non-bf16 input, bias, "
                       "grad enabled or CPU input)")
