@@ -56,7 +56,10 @@ def report(out, args):
               f"{r['GB/s']:>7.1f} GB/s  sol={r['sol']:<5}"
               f" {('%.0f TF/s' % r['TF/s']) if r['TF/s'] else ''}"
               + (f"  F.linear {r['f_linear_bf16_us']:.1f}us ratio "
-                 f"{r['ratio']}" if "ratio" in r else ""))
+                 f"{r['ratio']}" if "ratio" in r else "")
+              + (f"  +-{r['spread_us']}  skinny_fp8 {r['skinny_fp8_us']}us "
+                 f"bf16 {r['bf16_us']}us  beats_skinny={r['beats_skinny']}"
+                 if "beats_skinny" in r else ""))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
@@ -211,9 +214,110 @@ def mt_rows(out, dev="cuda"):
         del ws, sws
 
 
+LLAMA7B_SHAPES = (("qkv", 12288, 4096), ("o_proj", 4096, 4096),
+                  ("gate_up", 22016, 4096), ("down", 4096, 11008),
+                  ("lm_head", 32000, 4096))
+
+
+def _rounds(fns, rounds=3):
+    """Time the callables alternately, `rounds` rounds of timeit (median of
+    30 device-event timings after 10 warm-up calls) each. Per callable:
+    (median round, max - min over the rounds)."""
+    ts = [[] for _ in fns]
+    for _ in range(rounds):
+        for t, fn in zip(ts, fns):
+            t.append(timeit(fn))
+    return [(sorted(t)[len(t) // 2], max(t) - min(t)) for t in ts]
+
+
+def _w8_sets(N, K, dev):
+    """>= 600 MB of random finite e4m3 weights (10 sets of 17-131 MB would
+    sit in the 256 MiB Infinity Cache): canonical bytes, the w8_swz copy
+    and f32 scales per set."""
+    e = ops.ext()
+    n8 = max(10, -(-600_000_000 // (N * K)))
+    canon, swz, scales = [], [], []
+    for _ in range(n8):
+        b = torch.randint(0, 256, (N, K), dtype=torch.uint8, device=dev)
+        b[(b & 0x7F) == 0x7F] = 0x38           # the two NaN codes -> 1.0
+        canon.append(b)
+        swz.append(e.w8_swizzle(b))
+        scales.append(torch.rand(N, device=dev) * 1e-3 + 1e-4)
+    return n8, canon, swz, scales
+
+
+def w8_rows(out, dev="cuda", sweep=False):
+    """csrc/decode_gemm_w8.hip (fp8 weight stream, MODEL_LOAD_IN_8BIT) at
+    the five llama2-7b decode shapes, M = 1 and 32, against
+    skinny_gemm_fp8 (the RB_DECODE_GEMM_W8=0 path) and bf16 decode_gemm in
+    the same process: the three are timed alternately, three rounds of
+    median-of-30 device-event timings; the row carries the median round
+    and `spread_us` = max - min of the round medians. >= 600 MB of fp8
+    weight sets and ten bf16 sets are rotated. GB/s is N*K + 4N bytes over
+    time. `beats_skinny`: faster than skinny_gemm_fp8 by more than the
+    larger of the two spreads. With `sweep`, instead: force_split 1..8 on
+    the two N = 4096 shapes at M = 32, timed the same way."""
+    bf16 = torch.bfloat16
+    e = ops.ext()
+    for name, N, K in LLAMA7B_SHAPES:
+        if sweep and N != 4096:
+            continue
+        n8, canon, swz, scales = _w8_sets(N, K, dev)
+        sws = [] if sweep else [
+            e.decode_swizzle_w(torch.randn(N, K, dtype=bf16, device=dev))
+            for _ in range(10)]
+        nbytes = N * K + 4 * N
+        for M in ((32,) if sweep else (1, 32)):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            sx = e.decode_swizzle_x(x)
+            i = [0]
+
+            def w8(split=-1):
+                i[0] += 1
+                j = i[0] % n8
+                return e.decode_gemm_w8(sx, swz[j], scales[j], M, N, K, split)
+
+            def skinny():
+                i[0] += 1
+                j = i[0] % n8
+                return e.skinny_gemm_fp8(x, canon[j], scales[j])
+
+            def dg():
+                i[0] += 1
+                return e.decode_gemm(sx, sws[i[0] % 10], M, N, K)
+
+            if sweep:
+                splits = (1, 2, 3, 4, 6, 8)
+                res = _rounds([lambda s=s: w8(s) for s in splits])
+                for s, (us, spread) in zip(splits, res):
+                    r = row(f"decode_gemm_w8 {name} split={s}",
+                            f"{M}x{N}x{K}", us, nbytes, flops=2 * M * N * K)
+                    r["spread_us"] = round(spread, 2)
+                    r["policy_split"] = e.decode_gemm_w8_split(N, K)
+                    out.append(r)
+                continue
+            (us, sp), (sk, sksp), (b, bsp) = _rounds([w8, skinny, dg])
+            r = row(f"decode_gemm_w8 {name}", f"{M}x{N}x{K}", us, nbytes,
+                    flops=2 * M * N * K)
+            r.update(spread_us=round(sp, 2), skinny_fp8_us=round(sk, 2),
+                     skinny_fp8_spread_us=round(sksp, 2),
+                     bf16_us=round(b, 2), bf16_spread_us=round(bsp, 2),
+                     vs_skinny_fp8=round(us / sk, 3),
+                     vs_bf16=round(us / b, 3),
+                     split=e.decode_gemm_w8_split(N, K),
+                     beats_skinny=bool(sk - us > max(sp, sksp)))
+            out.append(r)
+        del canon, swz, scales, sws
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default=None)
+    p.add_argument("--w8-only", action="store_true",
+                   help="only the decode_gemm_w8 vs skinny_gemm_fp8 / bf16 "
+                        "decode_gemm rows")
+    p.add_argument("--w8-sweep", action="store_true",
+                   help="only the decode_gemm_w8 force_split sweep")
     p.add_argument("--dg-tail-only", action="store_true",
                    help="only the decode GEMM ring-tail vs tail-loop rows")
     p.add_argument("--w4-gemm-only", action="store_true",
@@ -227,6 +331,9 @@ def main():
     dev = "cuda"
     bf16 = torch.bfloat16
     out = []
+    if args.w8_only or args.w8_sweep:
+        w8_rows(out, dev, sweep=args.w8_sweep)
+        return report(out, args)
     if args.w4_gemm_only:
         w4_gemm_rows(out, dev)
         return report(out, args)
@@ -501,6 +608,8 @@ def main():
     us = timeit(fp8)
     out.append(row("skinny_fp8_decode", "32x12288x4096", us, 12288 * 4096,
                    flops=2 * 32 * 12288 * 4096))
+    del qs
+    w8_rows(out, dev)
 
     # train GEMM shapes (hipBLASLt, fresh weights)
     for M, N, K in [(2048, 4096, 4096), (2048, 11008, 4096),

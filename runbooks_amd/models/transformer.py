@@ -808,20 +808,27 @@ def fuse_for_inference(model: "Transformer",
     if load_in_8bit and torch.cuda.is_available():
         # MODEL_LOAD_IN_8BIT: decode weights additionally stored as OCP
         # e4m3 + per-channel scales — the decode GEMM streams half the
-        # bytes (ops/csrc/skinny_gemm.hip fp8 path). bf16 masters stay for
-        # prefill/big-M GEMMs: 288 GB HBM3E makes both-copies the right
-        # trade on MI355X.
-        from ..ops.linear import quantize_fp8
+        # bytes. RB_DECODE_GEMM_W8 on: the weight-stream kernel
+        # ops/csrc/decode_gemm_w8.hip and every shape it supports; off:
+        # ops/csrc/skinny_gemm.hip's fp8 tile kernel and its N % 64 /
+        # K % 256 gate. bf16 masters stay for prefill/big-M GEMMs: 288 GB
+        # HBM3E makes both-copies the right trade on MI355X.
+        from ..ops.linear import decode_gemm_w8_enabled, quantize_fp8
+        if decode_gemm_w8_enabled() and ops.has_hip():
+            def fp8_ok(w):
+                return ops.ext().decode_gemm_w8_supported(
+                    32, w.shape[0], w.shape[1])
+        else:
+            def fp8_ok(w):
+                return w.shape[0] % 64 == 0 and w.shape[1] % 256 == 0
         for blk in model.blocks:
             for w in (getattr(blk.attn, "_qkv_w", None),
                       getattr(blk.mlp, "_gateup_w", None),
                       blk.attn.o_proj.weight,
                       blk.mlp.down_proj.weight):
-                if w is not None and w.shape[0] % 64 == 0 and \
-                        w.shape[1] % 256 == 0:
+                if w is not None and fp8_ok(w):
                     quantize_fp8(w)
-        if model.lm_head.weight.shape[0] % 64 == 0 and \
-                model.lm_head.weight.shape[1] % 256 == 0:
+        if fp8_ok(model.lm_head.weight):
             quantize_fp8(model.lm_head.weight)
 
     if load_in_4bit and torch.cuda.is_available():

@@ -14,6 +14,7 @@ from .attention import (causal_attention, flash_prefill, paged_decode,  # noqa: 
                         paged_prefill_ref, paged_verify, paged_verify_ref)
 from .kvcache import BLOCK_SIZE, alloc_kv_cache, kv_append, kv_append_ref  # noqa: F401
 from .linear import (Linear, decode_gemm_mt, decode_gemm_mt_enabled,  # noqa: F401
+                     decode_gemm_w8, decode_gemm_w8_enabled,
                      decode_layout, decode_linear_glu,
                      decode_linear_raw, decode_linear_rope_append,
                      fast_linear, fused_epilogue_ok, w4_prefill_enabled)

@@ -95,6 +95,12 @@ at::Tensor decode_gemm_w4(at::Tensor xs, at::Tensor wq_swz, at::Tensor sc_swz,
                           int64_t tail);
 int64_t decode_gemm_w4_split(int64_t N, int64_t K);
 bool decode_gemm_w4_supported(int64_t M, int64_t N, int64_t K);
+at::Tensor w8_swizzle(at::Tensor w8);
+at::Tensor decode_gemm_w8(at::Tensor xs, at::Tensor w8_swz, at::Tensor scale,
+                          int64_t M, int64_t N, int64_t K, int64_t force_split,
+                          int64_t tail);
+int64_t decode_gemm_w8_split(int64_t N, int64_t K);
+bool decode_gemm_w8_supported(int64_t M, int64_t N, int64_t K);
 at::Tensor gemm_w4(at::Tensor x, at::Tensor wq_swz, at::Tensor sc_swz,
                    int64_t N, int64_t K);
 bool gemm_w4_supported(int64_t M, int64_t N, int64_t K);
@@ -244,6 +250,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tail") = -1);
   m.def("decode_gemm_w4_split", &decode_gemm_w4_split);
   m.def("decode_gemm_w4_supported", &decode_gemm_w4_supported);
+  m.def("w8_swizzle", &w8_swizzle,
+        "one-time canonical e4m3 bytes [N,K] -> fragment-lane-major layout");
+  m.def("decode_gemm_w8", &decode_gemm_w8,
+        "fp8-e4m3 weight-only weight-stream decode GEMM (f32 per-channel "
+        "scales): y[M<=32,N] = scale * (x @ e4m3(W8)^T) (bf16)",
+        py::arg("xs"), py::arg("w8_swz"), py::arg("scale"), py::arg("M"),
+        py::arg("N"), py::arg("K"), py::arg("force_split") = -1,
+        py::arg("tail") = -1);
+  m.def("decode_gemm_w8_split", &decode_gemm_w8_split);
+  m.def("decode_gemm_w8_supported", &decode_gemm_w8_supported);
   m.def("gemm_w4", &gemm_w4,
         "int4 weight-only MFMA GEMM, any M, over the decode kernel's stored "
         "copy: y[M,N] = x[M,K] @ dequant(Wq)^T (bf16)",

@@ -22,10 +22,26 @@ _USE_SKINNY = os.environ.get("RB_SKINNY_GEMM", "0") == "1"
 _USE_DECODE_GEMM = os.environ.get("RB_DECODE_GEMM", "1") == "1"
 
 
-# data_ptr(weight) -> (w8 uint8 view, f32 per-channel scale). Populated by
-# quantize_fp8 (serving with MODEL_LOAD_IN_8BIT); looked up on the decode
-# fast path.
-_FP8_REGISTRY: dict[int, tuple[torch.Tensor, torch.Tensor]] = {}
+# data_ptr(weight) -> (e4m3 bytes, f32 per-channel scale, swz, weakref to
+# the registered tensor). Populated by quantize_fp8 (serving with
+# MODEL_LOAD_IN_8BIT); looked up on the decode fast path. swz is None when
+# the bytes are the canonical [N, K] (csrc/skinny_gemm.hip's fp8 kernel),
+# (N, K) when they are csrc/decode_gemm_w8.hip's w8_swz layout. One byte per
+# weight stays resident, in whichever layout the chosen kernel reads: a
+# 70B model at 8 bit has no room for both.
+_FP8_REGISTRY: dict[int, tuple] = {}
+
+
+def decode_gemm_w8_enabled() -> bool:
+    """RB_DECODE_GEMM_W8 picks the fp8 decode kernel a weight is laid out
+    for, read when quantize_fp8 runs: 1 = the weight-stream kernel
+    csrc/decode_gemm_w8.hip, 0 = canonical bytes and skinny_gemm_fp8."""
+    return os.environ.get("RB_DECODE_GEMM_W8", _W8_DEFAULT) == "1"
+
+
+# Shipped default of RB_DECODE_GEMM_W8: profiles/README.md,
+# "decode_gemm_w8", has the ten (shape, M) cells that decide it.
+_W8_DEFAULT = "1"
 
 # data_ptr(weight) -> fragment-lane-major copy ([N/32][K/16][lane][8])
 # consumed by csrc/decode_gemm.hip. A second full-precision weight copy:
@@ -93,19 +109,63 @@ def quantize_fp8(weight: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Row-wise (per-output-channel) OCP e4m3 quantization; registers the
     pair so fast_linear dispatches to the fp8 decode GEMM. Pass the
     PERSISTENT tensor object (Parameter / fused buffer), not .data —
-    lookups verify identity via weakref."""
+    lookups verify identity via weakref.
+
+    Returns the canonical pair (e4m3 bytes [N, K] uint8, f32 scale [N]).
+    On a GPU tensor of a shape csrc/decode_gemm_w8.hip supports, with
+    RB_DECODE_GEMM_W8 on, the registry keeps that kernel's w8_swz layout
+    INSTEAD of the canonical bytes (which live on only while the caller
+    holds them); otherwise it keeps the canonical bytes. The cast
+    saturates, so no NaN code is ever emitted."""
     scale = weight.float().abs().amax(dim=1).clamp(min=1e-8) / E4M3_MAX
     w8 = (weight.float() / scale[:, None]).to(torch.float8_e4m3fn)
     w8_bytes = w8.view(torch.uint8).contiguous()
-    _FP8_REGISTRY[weight.data_ptr()] = (w8_bytes, scale.contiguous(),
+    scale = scale.contiguous()
+    for ptr in [p for p, e in _FP8_REGISTRY.items() if e[-1]() is None]:
+        del _FP8_REGISTRY[ptr]                 # purge dead entries
+    resident, swz = w8_bytes, None
+    if weight.dim() == 2 and decode_gemm_w8_enabled() and \
+            _backend.use_hip(weight):
+        ext = _backend.ext()
+        n, k = int(weight.shape[0]), int(weight.shape[1])
+        if ext.decode_gemm_w8_supported(32, n, k):
+            resident, swz = ext.w8_swizzle(w8_bytes), (n, k)
+    _FP8_REGISTRY[weight.data_ptr()] = (resident, scale, swz,
                                         weakref.ref(weight))
     return w8_bytes, scale
 
 
 def dequantize_fp8(w8_bytes: torch.Tensor, scale: torch.Tensor,
                    dtype=torch.bfloat16) -> torch.Tensor:
-    return (w8_bytes.view(torch.float8_e4m3fn).float() *
-            scale[:, None]).to(dtype)
+    """value(code) * scale from the canonical pair, multiplied in fp32 (in
+    fp64 for dtype=float64: e4m3 values and f32 scales are exact there, so
+    that is the decode kernels' exact weight) and cast to dtype."""
+    ct = torch.float64 if dtype == torch.float64 else torch.float32
+    return (w8_bytes.view(torch.float8_e4m3fn).to(ct) *
+            scale.to(ct)[:, None]).to(dtype)
+
+
+def _decode_gemm_w8(x, q, m, n, k):
+    # same operand contract as the bf16 v2 branch of fast_linear
+    xs = getattr(x, "_rb_swz", None)
+    if xs is None:
+        xs = _backend.ext().decode_swizzle_x(x.reshape(m, k).contiguous())
+    y = _backend.ext().decode_gemm_w8(xs, q[0], q[1], m, n, k)
+    return y.view(*x.shape[:-1], n)
+
+
+def decode_gemm_w8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """x [..., K] bf16 (1..32 rows) @ e4m3(weight)^T * scale through
+    csrc/decode_gemm_w8.hip on `weight`'s swizzled fp8 registration. Raises
+    when quantize_fp8 has not registered one (RB_DECODE_GEMM_W8=0, a CPU
+    weight, an unsupported shape) or the row count is unsupported."""
+    q = _registry_get(_FP8_REGISTRY, weight)
+    if q is None or q[2] is None:
+        raise RuntimeError("decode_gemm_w8: weight has no swizzled fp8 "
+                           "registration (quantize_fp8 on a GPU weight with "
+                           "RB_DECODE_GEMM_W8 on)")
+    n, k = q[2]
+    return _decode_gemm_w8(x, q, x.numel() // k, n, k)
 
 
 # data_ptr(weight) -> (wq_swz, sc_swz, (N, K), weakref to the registered
@@ -340,9 +400,13 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                     return y.view(*x.shape[:-1], n)
             if released:
                 _check_master(weight, "a GEMM without an int4 kernel")
-            if n % 64 == 0 and k % 256 == 0:
+            if _FP8_REGISTRY:
                 q = _registry_get(_FP8_REGISTRY, weight)
-                if q is not None:
+                if q is not None and q[2] is not None:
+                    # swizzled registration: every shape quantize_fp8
+                    # swizzles is one decode_gemm_w8 serves at m <= 32
+                    return _decode_gemm_w8(x, q, m, n, k)
+                if q is not None and n % 64 == 0 and k % 256 == 0:
                     y = _backend.ext().skinny_gemm_fp8(
                         x.reshape(m, k).contiguous(), q[0], q[1])
                     return y.view(*x.shape[:-1], n)
