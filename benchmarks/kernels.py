@@ -59,7 +59,11 @@ def report(out, args):
                  f"{r['ratio']}" if "ratio" in r else "")
               + (f"  +-{r['spread_us']}  skinny_fp8 {r['skinny_fp8_us']}us "
                  f"bf16 {r['bf16_us']}us  beats_skinny={r['beats_skinny']}"
-                 if "beats_skinny" in r else ""))
+                 if "beats_skinny" in r else "")
+              + (f"  wide {r['wide_us']}+-{r['wide_spread_us']} narrow "
+                 f"{r['narrow_us']}+-{r['narrow_spread_us']} "
+                 f"narrow_wins={r['narrow_wins']}"
+                 if "narrow_wins" in r else ""))
     if args.out:
         with open(args.out, "w") as f:
             json.dump(out, f, indent=1)
@@ -310,6 +314,54 @@ def w8_rows(out, dev="cuda", sweep=False):
         del canon, swz, scales, sws
 
 
+def w8_gemm_rows(out, dev="cuda"):
+    """csrc/gemm_w8.hip (fp8 weight-only, any M) at the five llama2-7b
+    shapes, both workgroup forms, against F.linear on a bf16 master
+    (hipBLASLt, what these GEMMs run on without RB_W8_PREFILL /
+    w8_resident) in the same process: wide, narrow and F.linear are timed
+    alternately, three rounds of median-of-30 device-event timings; the
+    row carries each one's median round and `*_spread_us` = max - min of
+    its round medians. >= 600 MB of fp8 sets and ten bf16 masters are
+    rotated. `ratio` = the policy's form / F.linear time (> 1: the fp8
+    GEMM is slower). `narrow_wins`: narrow beats wide by more than the
+    larger of the two spreads."""
+    bf16 = torch.bfloat16
+    e = ops.ext()
+    for name, N, K in LLAMA7B_SHAPES:
+        n8, canon, swz, scales = _w8_sets(N, K, dev)
+        del canon
+        ws = [torch.randn(N, K, dtype=bf16, device=dev) * 0.02
+              for _ in range(10)]
+        for M in (33, 64, 128, 160, 512, 2048):
+            x = torch.randn(M, K, dtype=bf16, device=dev)
+            i = [0]
+
+            def g8(form):
+                i[0] += 1
+                j = i[0] % n8
+                return e.gemm_w8(x, swz[j], scales[j], N, K, form)
+
+            def lin():
+                i[0] += 1
+                return torch.nn.functional.linear(x, ws[i[0] % 10])
+
+            (w, wsp), (n, nsp), (l, lsp) = _rounds(
+                [lambda: g8(0), lambda: g8(1), lin])
+            form = e.gemm_w8_form(M, N)
+            us = n if form else w
+            r = row(f"gemm_w8 {name}", f"{M}x{N}x{K}", us,
+                    N * K + 4 * N + (M * K + M * N) * 2, flops=2 * M * N * K)
+            r.update(policy_form=form, wide_us=round(w, 2),
+                     wide_spread_us=round(wsp, 2), narrow_us=round(n, 2),
+                     narrow_spread_us=round(nsp, 2),
+                     narrow_wins=bool(w - n > max(wsp, nsp)),
+                     f_linear_bf16_us=round(l, 2),
+                     f_linear_spread_us=round(lsp, 2),
+                     ratio=round(us / l, 2))
+            out.append(r)
+        del swz, scales, ws
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--out", default=None)
@@ -322,6 +374,8 @@ def main():
                    help="only the decode GEMM ring-tail vs tail-loop rows")
     p.add_argument("--w4-gemm-only", action="store_true",
                    help="only the gemm_w4 vs F.linear rows")
+    p.add_argument("--w8-gemm-only", action="store_true",
+                   help="only the gemm_w8 (both forms) vs F.linear rows")
     p.add_argument("--mt-only", action="store_true",
                    help="only the decode_gemm_mt vs F.linear rows")
     p.add_argument("--norm-only", action="store_true",
@@ -336,6 +390,9 @@ def main():
         return report(out, args)
     if args.w4_gemm_only:
         w4_gemm_rows(out, dev)
+        return report(out, args)
+    if args.w8_gemm_only:
+        w8_gemm_rows(out, dev)
         return report(out, args)
     if args.dg_tail_only:
         dg_tail_rows(out, dev)
@@ -610,6 +667,7 @@ def main():
                    flops=2 * 32 * 12288 * 4096))
     del qs
     w8_rows(out, dev)
+    w8_gemm_rows(out, dev)
 
     # train GEMM shapes (hipBLASLt, fresh weights)
     for M, N, K in [(2048, 4096, 4096), (2048, 11008, 4096),

@@ -662,13 +662,39 @@ def release_w4_masters(model: "Transformer") -> int:
     tied lm_head/embedding keeps its master: the embedding gather reads
     it. Returns the bytes released."""
     from ..ops.linear import release_w4_placeholder, w4_registered
+    return _release_masters(model, w4_registered, release_w4_placeholder,
+                            "_w4_resident")
+
+
+def release_w8_masters(model: "Transformer") -> int:
+    """Fp8-resident serving: release_w4_masters for a load_in_8bit model.
+    Every weight with a swizzled fp8 registration whose shape
+    csrc/gemm_w8.hip accepts (K % 64 == 0; a K % 64 == 32 weight keeps its
+    master) becomes a placeholder carrying the registration (ops/linear.py
+    _W8_RELEASED); its GEMMs then run csrc/decode_gemm_w8.hip (M <= 32) or
+    csrc/gemm_w8.hip. Returns the bytes released."""
+    from ..ops.linear import _w8_get, release_w8_placeholder
+    ext = ops.ext()
+
+    def releasable(w):
+        return _w8_get(w) is not None and ext.gemm_w8_supported(
+            32, w.shape[0], w.shape[1])
+    return _release_masters(model, releasable, release_w8_placeholder,
+                            "_w8_resident")
+
+
+def _release_masters(model, registered, placeholder,
+                     flag: str) -> int:
+    """The swap behind release_w4_masters / release_w8_masters: every
+    weight `registered` accepts -> `placeholder`'s stand-in;
+    sets model.<flag>."""
     released = 0
     first = []
 
     def swap(owner, attr, name, view=False):
         nonlocal released
         w = getattr(owner, attr)
-        ph = release_w4_placeholder(w, name, view=view)
+        ph = placeholder(w, name, view=view)
         setattr(owner, attr, ph)
         first.append(ph)
         if not view:
@@ -677,23 +703,23 @@ def release_w4_masters(model: "Transformer") -> int:
     for i, blk in enumerate(model.blocks):
         attn, mlp = blk.attn, blk.mlp
         w = getattr(attn, "_qkv_w", None)
-        if w is not None and w4_registered(w):
+        if w is not None and registered(w):
             swap(attn, "_qkv_w", f"blocks.{i}.attn.qkv (fused)")
             for proj in ("q_proj", "k_proj", "v_proj"):
                 swap(getattr(attn, proj), "weight",
                      f"blocks.{i}.attn.{proj}.weight", view=True)
         w = getattr(mlp, "_gateup_w", None)
-        if w is not None and w4_registered(w):
+        if w is not None and registered(w):
             swap(mlp, "_gateup_w", f"blocks.{i}.mlp.gate_up (fused)")
             for proj in ("gate_proj", "up_proj"):
                 swap(getattr(mlp, proj), "weight",
                      f"blocks.{i}.mlp.{proj}.weight", view=True)
-        if w4_registered(attn.o_proj.weight):
+        if registered(attn.o_proj.weight):
             swap(attn.o_proj, "weight", f"blocks.{i}.attn.o_proj.weight")
-        if w4_registered(mlp.down_proj.weight):
+        if registered(mlp.down_proj.weight):
             swap(mlp.down_proj, "weight", f"blocks.{i}.mlp.down_proj.weight")
     if model.lm_head.weight is not model.embed.weight and \
-            w4_registered(model.lm_head.weight):
+            registered(model.lm_head.weight):
         swap(model.lm_head, "weight", "lm_head.weight")
 
     if first:
@@ -703,7 +729,7 @@ def release_w4_masters(model: "Transformer") -> int:
             _check_master(first[0], "state_dict() / checkpoint save")
 
         model.register_state_dict_pre_hook(refuse_state_dict)
-        model._w4_resident = True
+        setattr(model, flag, True)
         if torch.cuda.is_available():
             # hand the freed blocks back so the engine's KV-pool sizing
             # sees them as free memory
@@ -714,7 +740,8 @@ def release_w4_masters(model: "Transformer") -> int:
 def fuse_for_inference(model: "Transformer",
                        load_in_8bit: bool = False,
                        load_in_4bit: bool = False,
-                       w4_resident: bool = False) -> "Transformer":
+                       w4_resident: bool = False,
+                       w8_resident: bool = False) -> "Transformer":
     """Fuse each block's QKV and gate/up weights into single tensors for
     serving: one wide GEMM per group instead of 2-3 skinny ones (the
     batch-<=32 decode GEMMs are weight-bandwidth bound, and hipBLASLt is
@@ -725,7 +752,9 @@ def fuse_for_inference(model: "Transformer",
     ``w4_resident`` (with ``load_in_4bit``, on a GPU) drops the bf16
     masters of the int4-quantized weights afterwards
     (release_w4_masters): the model then serves from its int4 copies
-    alone and can no longer train or save a checkpoint.
+    alone and can no longer train or save a checkpoint. ``w8_resident``
+    is the same for ``load_in_8bit`` (release_w8_masters): fp8 copies
+    alone, with RB_DECODE_GEMM_W8 on.
     """
     for blk in model.blocks:
         attn = blk.attn
@@ -812,7 +841,10 @@ def fuse_for_inference(model: "Transformer",
         # ops/csrc/decode_gemm_w8.hip and every shape it supports; off:
         # ops/csrc/skinny_gemm.hip's fp8 tile kernel and its N % 64 /
         # K % 256 gate. bf16 masters stay for prefill/big-M GEMMs: 288 GB
-        # HBM3E makes both-copies the right trade on MI355X.
+        # HBM3E makes both-copies the right trade on MI355X, unless
+        # w8_resident drops them: m > 32 then runs ops/csrc/gemm_w8.hip on
+        # the same fp8 copy (llama2-70b: ~140 GB of masters, by parameter
+        # count).
         from ..ops.linear import decode_gemm_w8_enabled, quantize_fp8
         if decode_gemm_w8_enabled() and ops.has_hip():
             def fp8_ok(w):
@@ -830,6 +862,8 @@ def fuse_for_inference(model: "Transformer",
                     quantize_fp8(w)
         if fp8_ok(model.lm_head.weight):
             quantize_fp8(model.lm_head.weight)
+        if w8_resident and decode_gemm_w8_enabled() and ops.has_hip():
+            release_w8_masters(model)
 
     if load_in_4bit and torch.cuda.is_available():
         # MODEL_LOAD_IN_4BIT: the same decode weight set additionally

@@ -17,7 +17,8 @@ from .linear import (Linear, decode_gemm_mt, decode_gemm_mt_enabled,  # noqa: F4
                      decode_gemm_w8, decode_gemm_w8_enabled,
                      decode_layout, decode_linear_glu,
                      decode_linear_raw, decode_linear_rope_append,
-                     fast_linear, fused_epilogue_ok, w4_prefill_enabled)
+                     fast_linear, fused_epilogue_ok, gemm_w8,
+                     w4_prefill_enabled, w8_prefill_enabled)
 from .lora_serve import (lora_expand_, lora_expand_ref_, lora_shrink,  # noqa: F401
                          lora_shrink_ref)
 from .norm import RMSNorm, rmsnorm, rmsnorm_ref  # noqa: F401

@@ -104,6 +104,10 @@ bool decode_gemm_w8_supported(int64_t M, int64_t N, int64_t K);
 at::Tensor gemm_w4(at::Tensor x, at::Tensor wq_swz, at::Tensor sc_swz,
                    int64_t N, int64_t K);
 bool gemm_w4_supported(int64_t M, int64_t N, int64_t K);
+at::Tensor gemm_w8(at::Tensor x, at::Tensor w8_swz, at::Tensor scale,
+                   int64_t N, int64_t K, int64_t form);
+bool gemm_w8_supported(int64_t M, int64_t N, int64_t K);
+int64_t gemm_w8_form(int64_t M, int64_t N);
 int64_t skinny_gemm_mmax();
 at::Tensor qkv_rope_append(at::Tensor y, at::Tensor cos, at::Tensor sin,
                            at::Tensor positions, at::Tensor k_cache,
@@ -266,6 +270,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("wq_swz"), py::arg("sc_swz"), py::arg("N"),
         py::arg("K"));
   m.def("gemm_w4_supported", &gemm_w4_supported);
+  m.def("gemm_w8", &gemm_w8,
+        "fp8-e4m3 weight-only MFMA GEMM, any M, over the decode kernel's "
+        "stored copy: y[M,N] = scale * (x[M,K] @ e4m3(W8)^T) (bf16); form "
+        "-1 = gemm_w8_form, 0 = wide, 1 = narrow workgroups (same bits)",
+        py::arg("x"), py::arg("w8_swz"), py::arg("scale"), py::arg("N"),
+        py::arg("K"), py::arg("form") = -1);
+  m.def("gemm_w8_supported", &gemm_w8_supported);
+  m.def("gemm_w8_form", &gemm_w8_form);
   m.def("qkv_rope_append", &qkv_rope_append,
         "packed qkv -> rope'd q + rope'd k / v appended to the paged cache");
   m.def("swiglu_packed", &swiglu_packed,

@@ -63,9 +63,9 @@
 // of W in flight. U = 6 has not been timed.
 //
 // Out of scope here: fused SwiGLU / RoPE-append epilogues for fp8, the
-// slab hand-off to the rmsnorm, an fp8 GEMM for M > 32 (those rows run
-// F.linear on the bf16 master), and quantizing activations to use the fp8
-// MFMA - this is weight-only by design.
+// slab hand-off to the rmsnorm, and quantizing activations to use the fp8
+// MFMA - this is weight-only by design. M > 32 on the same resident copy
+// is gemm_w8.hip.
 //
 // Fragment maps: see decode_gemm.hip (A = W, so C cols = m).
 
@@ -75,16 +75,13 @@
 #include <ATen/hip/HIPContext.h>
 
 #include "common.h"
+#include "w8_dequant.h"
 
 namespace {
 
 constexpr int BLOCK = 256;   // 4 waves
 constexpr int MMAX = 32;
 constexpr int U = 4;         // blocks (of 32 k) per ring half: 2x4 KiB W/wave
-
-// The epilogues add and scale adjacent floats, which the compiler would
-// fuse into packed-fp32 VALU ops; the kernels here are built without them.
-#define RB_W8_NO_PK __attribute__((target("no-packed-fp32-ops")))
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8v;
 typedef __attribute__((ext_vector_type(16))) float f32x16v;
@@ -96,27 +93,8 @@ __device__ __forceinline__ bf16x8v load8v(const uint16_t *p) {
   return c.v;
 }
 
-// two e4m3 codes (the low or high half of w) -> one dword of two bf16: the
-// conversion to f32 is exact and so is dropping the 16 low (zero) bits.
-// Byte selector: 2,3 = the high half of the second operand, 6,7 = of the
-// first.
-template <bool HI>
-__device__ __forceinline__ uint32_t w8_pair(uint32_t w) {
-  const auto f = __builtin_amdgcn_cvt_pk_f32_fp8(w, HI);
-  const float lo = f[0], up = f[1];
-  return __builtin_amdgcn_perm(__float_as_uint(up), __float_as_uint(lo),
-                               0x07060302u);
-}
-
-// 8 codes (bytes 0..3 of w0, then of w1) -> 8 bf16 A-fragment elements
-__device__ __forceinline__ bf16x8v w8_dequant8(uint32_t w0, uint32_t w1) {
-  union { u32x4v u; bf16x8v v; } c;
-  c.u[0] = w8_pair<false>(w0);
-  c.u[1] = w8_pair<true>(w0);
-  c.u[2] = w8_pair<false>(w1);
-  c.u[3] = w8_pair<true>(w1);
-  return c.v;
-}
+// e4m3 -> bf16 at use: w8_dequant.h, shared with gemm_w8.hip
+using rb::w8_dequant8;
 
 // One ring half = U blocks: raw weight bytes (nontemporal: streamed once,
 // must not evict L2) and the 2 x fragments per block (plain loads).

@@ -159,8 +159,8 @@ def decode_gemm_w8(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     csrc/decode_gemm_w8.hip on `weight`'s swizzled fp8 registration. Raises
     when quantize_fp8 has not registered one (RB_DECODE_GEMM_W8=0, a CPU
     weight, an unsupported shape) or the row count is unsupported."""
-    q = _registry_get(_FP8_REGISTRY, weight)
-    if q is None or q[2] is None:
+    q = _w8_get(weight)
+    if q is None:
         raise RuntimeError("decode_gemm_w8: weight has no swizzled fp8 "
                            "registration (quantize_fp8 on a GPU weight with "
                            "RB_DECODE_GEMM_W8 on)")
@@ -184,6 +184,28 @@ W4_GROUP = 64
 # others. wq_swz / sc_swz are None for a released VIEW of a fused weight
 # (q_proj.weight ...), which has no int4 copy of its own.
 _W4_RELEASED: dict[int, tuple] = {}
+
+# The same for fp8-resident serving (release_w8_masters): id(placeholder) ->
+# (w8_swz, scale, (N, K), name, weakref to the placeholder). Fields 0..2
+# sit where a swizzled _FP8_REGISTRY entry has them, so the fp8 kernels'
+# callers take either kind of entry.
+_W8_RELEASED: dict[int, tuple] = {}
+
+# released dict -> (format, switch) as the error texts name them
+_RESIDENT_KIND = ((_W4_RELEASED, "int4", "w4_resident"),
+                  (_W8_RELEASED, "fp8", "w8_resident"))
+
+
+def w8_prefill_enabled() -> bool:
+    """RB_W8_PREFILL=1 sends M > 32 GEMMs on a weight with a swizzled fp8
+    registration to csrc/gemm_w8.hip instead of F.linear on the bf16
+    master. Off by default; forced on while an fp8-resident model is alive
+    (its masters are gone)."""
+    if os.environ.get("RB_W8_PREFILL", "0") == "1":
+        return True
+    if _W8_RELEASED:
+        _purge_released()
+    return bool(_W8_RELEASED)
 
 
 def w4_prefill_enabled() -> bool:
@@ -235,23 +257,39 @@ def decode_gemm_mt(x: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
     return _decode_gemm_mt(x, dw, x.numel() // k, n, k)
 
 
-def _released_get(weight: torch.Tensor):
-    entry = _W4_RELEASED.get(id(weight))
-    if entry is None or entry[-1]() is not weight:
-        return None
-    return entry
+def _released_get(weight: torch.Tensor, released: dict | None = None):
+    """The placeholder's entry in `released` (default: in either released
+    dict), None when it has none."""
+    for rel in ((released,) if released is not None
+                else (_W4_RELEASED, _W8_RELEASED)):
+        entry = rel.get(id(weight))
+        if entry is not None and entry[-1]() is weight:
+            return entry
+    return None
+
+
+def _released_kind(weight: torch.Tensor) -> tuple[str, str]:
+    """("int4", "w4_resident") or ("fp8", "w8_resident") for a placeholder;
+    the int4 pair for a meta tensor nobody released."""
+    for rel, fmt, switch in _RESIDENT_KIND[1:]:
+        if _released_get(weight, rel) is not None:
+            return fmt, switch
+    return _RESIDENT_KIND[0][1:]
 
 
 def _check_master(weight: torch.Tensor, what: str) -> None:
-    """Raise instead of reading a released (placeholder) master."""
+    """Raise instead of reading a released (placeholder) master. `{fmt}` in
+    `what` becomes the resident format, int4 or fp8."""
     if weight.device.type != "meta":
         return
     entry = _released_get(weight)
     name = entry[3] if entry is not None else "<unnamed>"
+    fmt, switch = _released_kind(weight)
     raise RuntimeError(
-        f"weight {name} {tuple(weight.shape)}: the model is int4-resident "
-        f"(w4_resident), its bf16 master was released and {what} needs it. "
-        "Only bf16, bias-free, no-grad inference runs on an int4-resident "
+        f"weight {name} {tuple(weight.shape)}: the model is {fmt}-resident "
+        f"({switch}), its bf16 master was released and "
+        f"{what.format(fmt=fmt)} needs it. "
+        f"Only bf16, bias-free, no-grad inference runs on an {fmt}-resident "
         "model")
 
 
@@ -259,21 +297,54 @@ def _w4_get(weight: torch.Tensor):
     """(wq_swz, sc_swz, (N, K), ...) of an int4-registered weight, released
     or not; None without one."""
     if weight.device.type == "meta":
-        entry = _released_get(weight)
+        entry = _released_get(weight, _W4_RELEASED)
         return entry if entry is not None and entry[0] is not None else None
     if not _W4_REGISTRY:
         return None
     return _registry_get(_W4_REGISTRY, weight)
 
 
+def _w8_get(weight: torch.Tensor):
+    """(w8_swz, scale, (N, K), ...) of a weight with a swizzled fp8
+    registration, released or not; None without one."""
+    if weight.device.type == "meta":
+        entry = _released_get(weight, _W8_RELEASED)
+        return entry if entry is not None and entry[0] is not None else None
+    if not _FP8_REGISTRY:
+        return None
+    q = _registry_get(_FP8_REGISTRY, weight)
+    return q if q is not None and q[2] is not None else None
+
+
 def _purge_released() -> None:
-    for key in [k for k, e in _W4_RELEASED.items() if e[-1]() is None]:
-        del _W4_RELEASED[key]
+    for rel, _, _ in _RESIDENT_KIND:
+        for key in [k for k, e in rel.items() if e[-1]() is None]:
+            del rel[key]
 
 
 def w4_registered(weight: torch.Tensor) -> bool:
     """True when `weight` (released or not) has an int4 kernel copy."""
     return _w4_get(weight) is not None
+
+
+def _release_placeholder(weight, name, view, registry, released, entry,
+                         who):
+    _purge_released()
+    if entry is None and not view:
+        raise RuntimeError(f"{who}: {name} has no "
+                           f"{'int4' if released is _W4_RELEASED else 'fp8'}"
+                           " registration")
+    ph = torch.empty(weight.shape, dtype=weight.dtype, device="meta")
+    if isinstance(weight, torch.nn.Parameter):
+        ph = torch.nn.Parameter(ph, requires_grad=False)
+    if entry is not None:
+        del registry[weight.data_ptr()]
+        released[id(ph)] = (entry[0], entry[1], entry[2], name,
+                            weakref.ref(ph))
+    else:
+        released[id(ph)] = (None, None, tuple(weight.shape), name,
+                            weakref.ref(ph))
+    return ph
 
 
 def release_w4_placeholder(weight: torch.Tensor, name: str,
@@ -285,22 +356,21 @@ def release_w4_placeholder(weight: torch.Tensor, name: str,
     data_ptr, so it is not looked up). The caller swaps the placeholder in
     for every reference to `weight`; the master is freed when the last one
     goes."""
-    _purge_released()
     entry = None if view else _registry_get(_W4_REGISTRY, weight)
-    if entry is None and not view:
-        raise RuntimeError(f"release_w4_placeholder: {name} has no int4 "
-                           "registration")
-    ph = torch.empty(weight.shape, dtype=weight.dtype, device="meta")
-    if isinstance(weight, torch.nn.Parameter):
-        ph = torch.nn.Parameter(ph, requires_grad=False)
-    if entry is not None:
-        del _W4_REGISTRY[weight.data_ptr()]
-        _W4_RELEASED[id(ph)] = (entry[0], entry[1], entry[2], name,
-                                weakref.ref(ph))
-    else:
-        _W4_RELEASED[id(ph)] = (None, None, tuple(weight.shape), name,
-                                weakref.ref(ph))
-    return ph
+    return _release_placeholder(weight, name, view, _W4_REGISTRY,
+                                _W4_RELEASED, entry,
+                                "release_w4_placeholder")
+
+
+def release_w8_placeholder(weight: torch.Tensor, name: str,
+                           view: bool = False) -> torch.Tensor:
+    """release_w4_placeholder for a weight with a swizzled fp8
+    registration: the (w8_swz, scale, (N, K)) triple moves to the
+    placeholder, where fast_linear and decode_gemm_w8 find it."""
+    entry = None if view else _w8_get(weight)
+    return _release_placeholder(weight, name, view, _FP8_REGISTRY,
+                                _W8_RELEASED, entry,
+                                "release_w8_placeholder")
 
 
 def _w4_codes(weight: torch.Tensor):
@@ -376,6 +446,24 @@ def gemm_w4(x: torch.Tensor, q4) -> torch.Tensor:
     return y.view(*x.shape[:-1], n)
 
 
+def gemm_w8(x: torch.Tensor, q) -> torch.Tensor:
+    """x [..., K] bf16 @ e4m3(W)^T * scale through csrc/gemm_w8.hip (any M;
+    fast_linear uses it for M > 32). q is a swizzled fp8 entry (w8_swz,
+    scale, (N, K), ...) or the weight that carries one, released or not;
+    raises when the weight has none."""
+    if isinstance(q, torch.Tensor):
+        entry = _w8_get(q)
+        if entry is None:
+            raise RuntimeError("gemm_w8: weight has no swizzled fp8 "
+                               "registration (quantize_fp8 on a GPU weight "
+                               "with RB_DECODE_GEMM_W8 on)")
+        q = entry
+    n, k = q[2]
+    y = _backend.ext().gemm_w8(x.reshape(-1, k).contiguous(), q[0], q[1],
+                               n, k)
+    return y.view(*x.shape[:-1], n)
+
+
 def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                 bias: torch.Tensor | None = None) -> torch.Tensor:
     released = weight.device.type == "meta"
@@ -399,7 +487,10 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
                                                       m, n, k)
                     return y.view(*x.shape[:-1], n)
             if released:
-                _check_master(weight, "a GEMM without an int4 kernel")
+                q = _w8_get(weight)
+                if q is not None:
+                    return _decode_gemm_w8(x, q, m, n, k)
+                _check_master(weight, "a GEMM without an {fmt} kernel")
             if _FP8_REGISTRY:
                 q = _registry_get(_FP8_REGISTRY, weight)
                 if q is not None and q[2] is not None:
@@ -434,6 +525,13 @@ def fast_linear(x: torch.Tensor, weight: torch.Tensor,
             # batched prefill multiply by the weights decode streams
             if _backend.ext().gemm_w4_supported(m, n, k):
                 return gemm_w4(x, q4)
+        elif (_FP8_REGISTRY or released) and w8_prefill_enabled() and \
+                (q := _w8_get(weight)) is not None and \
+                _w4_get(weight) is None:
+            # fp8 weight-only GEMM at large M on the copy decode streams; a
+            # weight that also has an int4 registration keeps that route
+            if _backend.ext().gemm_w8_supported(m, n, k):
+                return gemm_w8(x, q)
         elif m <= DECODE_GEMM_MT_MAX_M and _USE_DECODE_GEMM and \
                 not released and decode_gemm_mt_enabled():
             # 33..256 rows are still a weight stream: same decode copy, one

@@ -125,6 +125,7 @@ class Engine:
                  prefill_chunk: int | None = None,
                  prefill_batch: int | None = None,
                  w4_resident: bool | None = None,
+                 w8_resident: bool | None = None,
                  batch_sampler: bool | None = None,
                  max_loras: int | None = None,
                  lora_rank: int | None = None,
@@ -159,6 +160,23 @@ class Engine:
                   + " (the bf16 master weights stay)", flush=True)
             w4_resident = False
         self.w4_resident = bool(w4_resident)
+        # Fp8-resident serving (RB_W8_RESIDENT=1 or w8_resident=True, with
+        # load_in_8bit and RB_DECODE_GEMM_W8 on): the same for the fp8
+        # copies; M > 32 runs ops/csrc/gemm_w8.hip.
+        if w8_resident is None:
+            w8_resident = _os1.environ.get("RB_W8_RESIDENT", "0") == "1"
+        if w8_resident:
+            from ..ops.linear import decode_gemm_w8_enabled
+            why = ("without a GPU" if not torch.cuda.is_available()
+                   else "at TP>1" if model.tp > 1
+                   else "without load_in_8bit" if not load_in_8bit
+                   else "with RB_DECODE_GEMM_W8 off"
+                   if not decode_gemm_w8_enabled() else None)
+            if why is not None:
+                print(f"engine: w8_resident ignored {why} (the bf16 master "
+                      "weights stay)", flush=True)
+                w8_resident = False
+        self.w8_resident = bool(w8_resident)
         if torch.cuda.is_available():
             # TP>1 included: each rank fuses ITS OWN qkv / gate-up weight
             # shards and registers decode-GEMM layouts for them — the
@@ -168,7 +186,8 @@ class Engine:
             fuse_for_inference(self.model,
                                load_in_8bit=load_in_8bit and model.tp == 1,
                                load_in_4bit=load_in_4bit and model.tp == 1,
-                               w4_resident=self.w4_resident)
+                               w4_resident=self.w4_resident,
+                               w8_resident=self.w8_resident)
         if load_in_4bit and model.tp > 1:
             print("engine: MODEL_LOAD_IN_4BIT ignored at TP>1 "
                   "(int4 decode path is single-GPU, like the fp8 one)",

@@ -14,6 +14,8 @@ examples/llama2-7b/server.yaml, container-contract.md:50-56) — loads
 - PARAM_W4_RESIDENT / W4_RESIDENT ("1" or "true", with MODEL_LOAD_IN_4BIT):
   drop the bf16 masters of the 4-bit weights; prefill runs the int4 GEMM
   and the freed memory becomes KV cache.
+- PARAM_W8_RESIDENT / W8_RESIDENT ("1" or "true", with MODEL_LOAD_IN_8BIT):
+  the same for the 8-bit weights; prefill runs the fp8 GEMM.
 - PARAM_BATCH_SAMPLER / BATCH_SAMPLER ("1" or "true"): sample each decode
   batch with the batched per-request sampler (one launch, one download);
   unset leaves the engine's RB_BATCH_SAMPLER default.
@@ -154,6 +156,8 @@ def main():
     resident = os.environ.get(
         "PARAM_W4_RESIDENT",
         os.environ.get("W4_RESIDENT", "")).lower() in ("1", "true")
+    # PARAM_W8_RESIDENT / W8_RESIDENT: the same for an 8-bit model
+    resident8 = (_env("W8_RESIDENT") or "").lower() in ("1", "true")
     # PARAM_BATCH_SAMPLER / BATCH_SAMPLER: sample every decode batch with
     # the one-launch per-request sampler (unset leaves RB_BATCH_SAMPLER)
     bsampler = os.environ.get(
@@ -168,6 +172,7 @@ def main():
     max_loras = int(_env("MAX_LORAS") or len(loras))
     engine = Engine(model, load_in_8bit=in_8bit, load_in_4bit=in_4bit,
                     kv_fp8=kv_fp8, w4_resident=resident or None,
+                    w8_resident=resident8 or None,
                     # unset leaves the engine's own RB_* env defaults
                     prefill_from_cache=from_cache or None,
                     prefill_chunk=chunk or None,
