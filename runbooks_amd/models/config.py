@@ -28,9 +28,12 @@ class ModelConfig:
     rope_theta: float = 10000.0
     parallel_residual: bool = False  # falcon-style attn+mlp parallel block
     single_norm: bool = False        # falcon-7b: one shared ln for attn+mlp
-    # sliding-window attention width (mistral). Enforced by the serving
-    # engine at BLOCK_SIZE granularity (up to BLOCK_SIZE-1 extra tokens
-    # of context vs the strict window); expired KV blocks are freed.
+    # sliding-window attention width W (mistral): a query sees its last W
+    # tokens, itself included. Exact in the prefill paths (the kernels take
+    # W, also for prompts longer than W) and in decode (the serving engine
+    # frees expired KV blocks and passes strict starts). Not in
+    # Transformer.forward (training) nor in verify, so the engine ignores
+    # `speculative` for a windowed model.
     sliding_window: int | None = None
     tie_embeddings: bool = False
     mlp_bias: bool = False
@@ -91,8 +94,8 @@ register(ModelConfig("llama3-70b", vocab_size=128256, hidden_size=8192,
                      num_layers=80, num_heads=64, num_kv_heads=8,
                      intermediate_size=28672, max_seq_len=8192,
                      rope_theta=500000.0))
-# mistral-7b: llama-shaped GQA-8 with a 4k sliding window (the engine
-# enforces it block-aligned and frees expired KV blocks)
+# mistral-7b: llama-shaped GQA-8 with a 4k sliding window (exact in
+# prefill and decode up to max_seq_len; the engine frees expired KV blocks)
 register(ModelConfig("mistral-7b", vocab_size=32000, hidden_size=4096,
                      num_layers=32, num_heads=32, num_kv_heads=8,
                      intermediate_size=14336, max_seq_len=8192,

@@ -11,7 +11,8 @@ One implementation, three family knobs (ModelConfig):
 Forward modes:
   * ``forward(tokens)``             — training, full causal attention
   * ``prefill(...)``                — fills the paged KV cache, returns
-                                      last-position logits
+                                      last-position logits (this and the
+                                      two below honour cfg.sliding_window)
   * ``prefill_paged(...)``          — one chunk of one prompt whose earlier
                                       positions are already in the cache
   * ``prefill_paged_batch(...)``    — the same for several prompts' chunks
@@ -126,7 +127,8 @@ class Attention(nn.Module):
         ops.kv_append(k, v, kc, vc, slot_mapping)
         q = q.view(B, S, self.hq, self.dh)
         o = ops.flash_prefill(q, k.view(B, S, self.hkv, self.dh),
-                              v.view(B, S, self.hkv, self.dh), scale=self.scale)
+                              v.view(B, S, self.hkv, self.dh), scale=self.scale,
+                              window=self.cfg.sliding_window or 0)
         if lora is not None:
             return self._o_lora(o.reshape(B * S, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(B * S, self.hq * self.dh))
@@ -140,7 +142,8 @@ class Attention(nn.Module):
         q, k, v = self._qkv(x, cos, sin, positions, lora)
         ops.kv_append(k, v, kc, vc, slot_mapping)
         o = ops.paged_prefill(q, kc, vc, block_table, ctx_len,
-                              scale=self.scale)
+                              scale=self.scale,
+                              window=self.cfg.sliding_window or 0)
         if lora is not None:
             return self._o_lora(o.reshape(T, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(T, self.hq * self.dh))
@@ -155,7 +158,8 @@ class Attention(nn.Module):
         q, k, v = self._qkv(x, cos, sin, positions, lora)
         ops.kv_append(k, v, kc, vc, slot_mapping)
         o = ops.paged_prefill_batch(q, kc, vc, block_tables, plan,
-                                    scale=self.scale)
+                                    scale=self.scale,
+                                    window=self.cfg.sliding_window or 0)
         if lora is not None:
             return self._o_lora(o.reshape(T, self.hq * self.dh), lora)
         return self.o_proj(o.reshape(T, self.hq * self.dh))

@@ -18,6 +18,11 @@
 * ``paged_prefill_batch``: the same for several sequences' chunks packed
   into one token dimension, one launch; lengths come from a host-built
   ``paged_prefill_plan``.
+
+``flash_prefill`` and the two paged prefills take ``window`` (sliding-window
+attention, mistral): with ``window = W >= 1`` the query at position p sees
+the W keys ``p - W < j <= p``; 0 means no window. On the GPU that is the
+windowed instantiation of the same kernels (csrc/flash_fwd_core.h).
 """
 from __future__ import annotations
 
@@ -76,10 +81,19 @@ def causal_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     return causal_attention_ref(q, k, v, scale=scale, q_block=q_block)
 
 
+def _check_window(window) -> int:
+    window = int(window)
+    if window < 0:
+        raise ValueError(f"window must be >= 0, got {window}")
+    return window
+
+
 def causal_attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                          scale: float | None = None,
-                         q_block: int = 256) -> torch.Tensor:
-    """Chunked eager reference (fp32 softmax), differentiable."""
+                         q_block: int = 256, window: int = 0) -> torch.Tensor:
+    """Chunked eager reference (fp32 softmax), differentiable. ``window``
+    = W >= 1 also masks keys j <= p - W of the row at position p."""
+    window = _check_window(window)
     B, S, Hq, Dh = q.shape
     Hkv = k.shape[2]
     if scale is None:
@@ -99,6 +113,8 @@ def causal_attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
         scores = torch.matmul(qb, kt[:, :, :s1].transpose(-1, -2)).float() * scale
         mask = torch.ones(s1 - s0, s1, dtype=torch.bool, device=q.device)
         mask = torch.triu(mask, diagonal=s0 + 1)
+        if window:
+            mask |= torch.tril(torch.ones_like(mask), diagonal=s0 - window)
         scores = scores.masked_fill(mask, float("-inf"))
         p = torch.softmax(scores, dim=-1).to(vt.dtype)
         outs.append(torch.matmul(p, vt[:, :, :s1]))
@@ -106,19 +122,23 @@ def causal_attention_ref(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
 
 
 def flash_prefill(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                  scale: float | None = None) -> torch.Tensor:
+                  scale: float | None = None, window: int = 0) -> torch.Tensor:
     """Causal GQA attention, inference-only (no autograd).
 
     q [B, S, Hq, Dh] bf16 on GPU -> gfx950 MFMA flash kernel
     (csrc/attention_prefill.hip); CPU falls back to the chunked reference.
+    ``window`` = W >= 1: sliding-window attention, the row at position p
+    sees the W keys p - W < j <= p (0: plain causal).
     """
+    window = _check_window(window)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _backend.use_hip(q) and q.shape[-1] in (64, 128, 256) \
             and q.dtype == torch.bfloat16:
         return _backend.ext().flash_prefill(
-            q.contiguous(), k.contiguous(), v.contiguous(), float(scale))
-    return causal_attention_ref(q, k, v, scale=scale)
+            q.contiguous(), k.contiguous(), v.contiguous(), float(scale),
+            window)
+    return causal_attention_ref(q, k, v, scale=scale, window=window)
 
 
 def paged_decode_ref(q, k_cache, v_cache, block_tables, seq_lens, scale,
@@ -156,11 +176,14 @@ def paged_decode_ref(q, k_cache, v_cache, block_tables, seq_lens, scale,
     return out
 
 
-def paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale=None):
+def paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale=None,
+                      window: int = 0):
     """fp32 reference for paged_prefill: gather keys [0, ctx_len + T) from
     the cache (plain or transposed-V blocks; fp8 caches are dequantized up
-    front), then masked softmax — row r sees keys <= ctx_len + r.
+    front), then masked softmax — row r sees keys <= ctx_len + r, and with
+    ``window`` = W >= 1 only those > ctx_len + r - W.
     q [T, Hq, Dh] -> [T, Hq, Dh] in q's dtype."""
+    window = _check_window(window)
     if k_cache.dtype == torch.uint8:
         from .kvcache import fp8_dequant_cache_ref
         k_cache = fp8_dequant_cache_ref(k_cache)
@@ -187,20 +210,25 @@ def paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale=None):
     rows = torch.arange(T, device=q.device)[:, None] + ctx_len
     keys = torch.arange(n, device=q.device)[None, :]
     s = s.masked_fill(keys > rows, float("-inf"))
+    if window:
+        s = s.masked_fill(keys <= rows - window, float("-inf"))
     p = torch.softmax(s, dim=-1)
     return torch.einsum("htn,nhd->thd", p, v).to(q.dtype)
 
 
 def paged_prefill(q, k_cache, v_cache, block_table, ctx_len,
-                  scale: float | None = None):
+                  scale: float | None = None, window: int = 0):
     """Causal attention of one prompt chunk over the paged cache.
 
     q [T, Hq, Dh]: one sequence, row r at absolute position ctx_len + r.
     The chunk's own k/v must already be appended, so keys [0, ctx_len + T)
     are all read through ``block_table`` (int32 [>= ceil((ctx_len+T)/16)]).
     GPU: bf16 caches in either alloc_kv_cache layout run the gfx950 MFMA
-    kernel; fp8 caches raise. CPU: fp32 reference.
+    kernel; fp8 caches raise. CPU: fp32 reference. ``window`` = W >= 1: row
+    r sees only the W keys above ctx_len + r - W; the kernel then never
+    reads ``block_table`` below entry 4 * (max(0, ctx_len - W + 1) // 64).
     """
+    window = _check_window(window)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _backend.use_hip(q):
@@ -210,8 +238,9 @@ def paged_prefill(q, k_cache, v_cache, block_table, ctx_len,
         return _backend.ext().flash_prefill_paged(
             q.contiguous(), k_cache, v_cache,
             block_table.to(torch.int32).contiguous(), int(ctx_len),
-            float(scale))
-    return paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale)
+            float(scale), window)
+    return paged_prefill_ref(q, k_cache, v_cache, block_table, ctx_len, scale,
+                             window)
 
 
 class PagedPrefillPlan:
@@ -296,7 +325,7 @@ def _check_batch_shapes(q, block_tables, plan):
 
 
 def paged_prefill_batch_ref(q, k_cache, v_cache, block_tables, plan,
-                            scale=None):
+                            scale=None, window: int = 0):
     """fp32 reference for paged_prefill_batch: paged_prefill_ref on each
     sequence's rows, table row and context length."""
     _check_batch_shapes(q, block_tables, plan)
@@ -305,12 +334,12 @@ def paged_prefill_batch_ref(q, k_cache, v_cache, block_tables, plan,
         lo, hi = plan.cu_q[b], plan.cu_q[b + 1]
         out[lo:hi] = paged_prefill_ref(q[lo:hi], k_cache, v_cache,
                                        block_tables[b], plan.ctx_lens[b],
-                                       scale)
+                                       scale, window)
     return out
 
 
 def paged_prefill_batch(q, k_cache, v_cache, block_tables, plan,
-                        scale: float | None = None):
+                        scale: float | None = None, window: int = 0):
     """Causal attention of several sequences' prompt chunks, packed back to
     back in q [Ttot, Hq, Dh], over the paged cache in one launch.
 
@@ -320,8 +349,10 @@ def paged_prefill_batch(q, k_cache, v_cache, block_tables, plan,
     are never read. Every chunk's own k/v must already be appended. GPU:
     the gfx950 MFMA kernel, each sequence bit-identical to ``paged_prefill``
     on it alone; all lengths are checked on the host, nothing waits for the
-    device. fp8 caches raise. CPU: fp32 reference.
+    device. fp8 caches raise. CPU: fp32 reference. ``window``: the sliding
+    window of ``paged_prefill``, the same for every sequence.
     """
+    window = _check_window(window)
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     if _backend.use_hip(q):
@@ -336,9 +367,9 @@ def paged_prefill_batch(q, k_cache, v_cache, block_tables, plan,
             block_tables = block_tables.to(torch.int32)
         return _backend.ext().flash_prefill_paged_batch(
             q.contiguous(), k_cache, v_cache, block_tables.contiguous(),
-            plan.dev, plan.cpu, plan.num_seqs, float(scale))
+            plan.dev, plan.cpu, plan.num_seqs, float(scale), window)
     return paged_prefill_batch_ref(q, k_cache, v_cache, block_tables, plan,
-                                   scale)
+                                   scale, window)
 
 
 VERIFY_MAX_T = 8

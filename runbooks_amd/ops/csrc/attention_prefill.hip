@@ -7,6 +7,8 @@
 // and the MFMA layout probe.
 //
 // q,k,v,out: [B, S, H, DH] bf16 token-major. DH in {64, 128, 256}.
+// flash_prefill takes a sliding window (WIN instantiations, flash_fwd_core.h);
+// the training forward does not.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -77,21 +79,24 @@ struct DenseKV {
   }
 };
 
-template <int DH>
+// WIN: sliding window, row p sees keys (p - window, p] (flash_fwd_core.h);
+// window is ignored without it.
+template <int DH, bool WIN>
 __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_kernel(
     const uint16_t *__restrict__ qp, const uint16_t *__restrict__ kp,
     const uint16_t *__restrict__ vp, uint16_t *__restrict__ op,
     float *__restrict__ lsep,  // [B, Hq, S] log-sum-exp for training bwd
-    int B, int S, int Hq, int Hkv, float scale) {
+    int B, int S, int Hq, int Hkv, float scale, int window) {
   const int q0 = blockIdx.x * 256;
   const int h = blockIdx.y;
   const int b = blockIdx.z;
   const int qrow = q0 + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
   const bool q_valid = qrow < S;
 
-  const auto acc = rb::flash_fwd_rows<DH>(
+  const auto acc = rb::flash_fwd_rows<DH, WIN>(
       qp + ((int64_t)(b * S + (q_valid ? qrow : 0)) * Hq + h) * DH, qrow,
-      q_valid, S, q0, DenseKV{kp, vp, b, S, Hkv, h / (Hq / Hkv)}, scale);
+      q_valid, S, q0, DenseKV{kp, vp, b, S, Hkv, h / (Hq / Hkv)}, scale,
+      window);
   if (q_valid)
     rb::flash_fwd_store<DH>(
         acc, op + ((int64_t)(b * S + qrow) * Hq + h) * DH,
@@ -101,7 +106,7 @@ __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_kernel(
 }  // namespace
 
 static at::Tensor flash_fwd_impl(at::Tensor q, at::Tensor k, at::Tensor v,
-                                 double scale, float *lsep) {
+                                 double scale, float *lsep, int64_t window) {
   TORCH_CHECK(q.is_cuda() && q.is_contiguous() && k.is_contiguous() &&
                   v.is_contiguous(), "flash_prefill: contiguous GPU tensors");
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "flash_prefill: bf16 only");
@@ -114,21 +119,25 @@ static at::Tensor flash_fwd_impl(at::Tensor q, at::Tensor k, at::Tensor v,
   auto stream = at::hip::getCurrentHIPStream();
   const dim3 grid((S + 255) / 256, Hq, B);
 
-  rb::flash_dispatch_dh(DH, "flash_prefill", [&](auto dh) {
+  rb::flash_dispatch_win(DH, window, S, "flash_prefill",
+                         [&](auto dh, auto win, int w) {
     constexpr int D = decltype(dh)::value;
-    hipLaunchKernelGGL((flash_prefill_kernel<D>), grid, dim3(BLOCK),
+    constexpr bool WIN = decltype(win)::value;
+    hipLaunchKernelGGL((flash_prefill_kernel<D, WIN>), grid, dim3(BLOCK),
                        rb::flash_fwd_smem<D>(), stream,
                        (const uint16_t *)q.data_ptr(),
                        (const uint16_t *)k.data_ptr(),
                        (const uint16_t *)v.data_ptr(), (uint16_t *)out.data_ptr(),
-                       lsep, B, S, Hq, Hkv, (float)scale);
+                       lsep, B, S, Hq, Hkv, (float)scale, w);
   });
   return out;
 }
 
+// window = W >= 1: sliding-window attention, row p sees the W keys
+// (p - W, p]; 0: plain causal.
 at::Tensor flash_prefill(at::Tensor q, at::Tensor k, at::Tensor v,
-                         double scale) {
-  return flash_fwd_impl(q, k, v, scale, nullptr);
+                         double scale, int64_t window) {
+  return flash_fwd_impl(q, k, v, scale, nullptr, window);
 }
 
 // Training forward: additionally returns the per-row log-sum-exp
@@ -137,7 +146,7 @@ std::vector<at::Tensor> flash_fwd_train(at::Tensor q, at::Tensor k,
                                         at::Tensor v, double scale) {
   const int B = (int)q.size(0), S = (int)q.size(1), Hq = (int)q.size(2);
   auto lse = at::empty({B, Hq, S}, q.options().dtype(at::kFloat));
-  auto out = flash_fwd_impl(q, k, v, scale, lse.data_ptr<float>());
+  auto out = flash_fwd_impl(q, k, v, scale, lse.data_ptr<float>(), 0);
   return {out, lse};
 }
 

@@ -24,6 +24,11 @@
 //  * keys >= ctx_len + T are zero-filled in LDS and never read from
 //    memory: stale cache contents may be anything, and 0 x NaN in the PV
 //    MFMA would poison the row.
+//  * with a sliding window (WIN, window = W: row p sees keys (p - W, p]) a
+//    workgroup stages from tile max(0, row0 - W + 1) / 64 on, so the table
+//    entries below 4 * (max(0, ctx_len - W + 1) / 64) are never read
+//    either. Keys of a staged tile in front of a row's window are the
+//    sequence's own (finite) keys: staged as they are, masked in S.
 //
 // q, out: [T, Hq, DH] bf16. k_cache: [blk, Hkv, 16, DH]. v_cache: the same,
 // or [blk, Hkv, DH, 16] (alloc_kv_cache v_transposed). DH in {64, 128, 256}.
@@ -149,11 +154,12 @@ struct PagedKV {
   }
 };
 
-template <int DH, bool VT>
+template <int DH, bool VT, bool WIN>
 __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_paged_kernel(
     const uint16_t *__restrict__ qp, const uint16_t *__restrict__ kcp,
     const uint16_t *__restrict__ vcp, const int *__restrict__ btp,
-    uint16_t *__restrict__ op, int T, int ctx, int Hq, int Hkv, float scale) {
+    uint16_t *__restrict__ op, int T, int ctx, int Hq, int Hkv, float scale,
+    int window) {
   const int S = ctx + T;                    // keys in the cache
   const int q0 = blockIdx.x * 256;          // first chunk row of this WG
   const int h = blockIdx.y;
@@ -162,12 +168,12 @@ __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_paged_kernel(
   const int crow = q0 + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
   const bool q_valid = crow < T;
 
-  const auto acc = rb::flash_fwd_rows<DH>(
+  const auto acc = rb::flash_fwd_rows<DH, WIN>(
       qp + ((int64_t)(q_valid ? crow : 0) * Hq + h) * DH, ctx + crow, q_valid,
       S, ctx + q0,
       PagedKV<VT>{kcp, vcp, btp, S, (int64_t)Hkv * CBS * DH,
                   (int64_t)h_kv * CBS * DH},
-      scale);
+      scale, window);
   if (q_valid)
     rb::flash_fwd_store<DH>(acc, op + ((int64_t)crow * Hq + h) * DH, nullptr);
 }
@@ -180,14 +186,14 @@ __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_paged_kernel(
 //   cu_q     [B + 1]  sequence b owns packed rows [cu_q[b], cu_q[b+1])
 //   ctx_lens [B]      keys cached before sequence b's chunk
 //   btp      [B][maxb] block tables; row b is read below ceil(S_b/16) only
-template <int DH, bool VT>
+template <int DH, bool VT, bool WIN>
 __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_paged_batch_kernel(
     const uint16_t *__restrict__ qp, const uint16_t *__restrict__ kcp,
     const uint16_t *__restrict__ vcp, const int *__restrict__ btp,
     uint16_t *__restrict__ op, const int *__restrict__ cu_q,
     const int *__restrict__ ctx_lens, const int *__restrict__ tile_seq,
     const int *__restrict__ tile_row0, int maxb, int Hq, int Hkv,
-    float scale) {
+    float scale, int window) {
   const int b = tile_seq[blockIdx.x];
   const int q0 = tile_row0[blockIdx.x];     // first chunk row of this WG
   const int qbeg = cu_q[b];
@@ -200,12 +206,12 @@ __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_paged_batch_kernel(
   const int crow = q0 + (threadIdx.x >> 6) * 32 + (threadIdx.x & 31);
   const bool q_valid = crow < T;
 
-  const auto acc = rb::flash_fwd_rows<DH>(
+  const auto acc = rb::flash_fwd_rows<DH, WIN>(
       qp + ((int64_t)(qbeg + (q_valid ? crow : 0)) * Hq + h) * DH, ctx + crow,
       q_valid, S, ctx + q0,
       PagedKV<VT>{kcp, vcp, btp + (int64_t)b * maxb, S,
                   (int64_t)Hkv * CBS * DH, (int64_t)h_kv * CBS * DH},
-      scale);
+      scale, window);
   if (q_valid)
     rb::flash_fwd_store<DH>(
         acc, op + ((int64_t)(qbeg + crow) * Hq + h) * DH, nullptr);
@@ -215,7 +221,8 @@ __global__ __launch_bounds__(BLOCK, 2) void flash_prefill_paged_batch_kernel(
 
 at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache,
                                at::Tensor v_cache, at::Tensor block_table,
-                               int64_t ctx_len, double scale) {
+                               int64_t ctx_len, double scale,
+                               int64_t window) {
   TORCH_CHECK(k_cache.scalar_type() != at::kByte &&
                   v_cache.scalar_type() != at::kByte,
               "flash_prefill_paged: fp8 KV caches are not supported");
@@ -252,10 +259,12 @@ at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache,
   auto out = at::empty_like(q);
   const dim3 grid((T + 255) / 256, Hq);
 
-  rb::flash_dispatch_dh(DH, "flash_prefill_paged", [&](auto dh) {
+  rb::flash_dispatch_win(DH, window, ctx_len + T, "flash_prefill_paged",
+                         [&](auto dh, auto win, int w) {
     constexpr int D = decltype(dh)::value;
-    auto kernel = vt ? flash_prefill_paged_kernel<D, true>
-                     : flash_prefill_paged_kernel<D, false>;
+    constexpr bool WIN = decltype(win)::value;
+    auto kernel = vt ? flash_prefill_paged_kernel<D, true, WIN>
+                     : flash_prefill_paged_kernel<D, false, WIN>;
     hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), rb::flash_fwd_smem<D>(),
                        at::hip::getCurrentHIPStream(),
                        (const uint16_t *)q.data_ptr(),
@@ -263,7 +272,7 @@ at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache,
                        (const uint16_t *)v_cache.data_ptr(),
                        (const int *)block_table.data_ptr(),
                        (uint16_t *)out.data_ptr(), (int)T, (int)ctx_len,
-                       (int)Hq, (int)Hkv, (float)scale);
+                       (int)Hq, (int)Hkv, (float)scale, w);
   });
   return out;
 }
@@ -277,7 +286,8 @@ at::Tensor flash_prefill_paged_batch(at::Tensor q, at::Tensor k_cache,
                                      at::Tensor v_cache,
                                      at::Tensor block_tables,
                                      at::Tensor plan_dev, at::Tensor plan_cpu,
-                                     int64_t B, double scale) {
+                                     int64_t B, double scale,
+                                     int64_t window) {
   const char *op = "flash_prefill_paged_batch";
   TORCH_CHECK(k_cache.scalar_type() != at::kByte &&
                   v_cache.scalar_type() != at::kByte,
@@ -323,9 +333,10 @@ at::Tensor flash_prefill_paged_batch(at::Tensor q, at::Tensor k_cache,
   const int64_t Hkv = k_cache.size(1);
   const int64_t maxb = block_tables.size(1);
   TORCH_CHECK(cu[0] == 0, op, ": malformed plan");
-  int64_t tile = 0;
+  int64_t tile = 0, max_keys = 0;  // max_keys: the longest sequence's keys
   for (int64_t b = 0; b < B; ++b) {
     const int64_t T = (int64_t)cu[b + 1] - cu[b], ctx = cx[b];
+    max_keys = std::max(max_keys, ctx + T);
     TORCH_CHECK(T >= 1 && ctx >= 0, op, ": T_b >= 1, ctx_b >= 0 (sequence ",
                 b, ": T ", T, ", ctx ", ctx, ")");
     TORCH_CHECK(ctx + T < (int64_t(1) << 30), op, ": sequence too long");
@@ -351,10 +362,12 @@ at::Tensor flash_prefill_paged_batch(at::Tensor q, at::Tensor k_cache,
   const dim3 grid(ntiles, Hq);
   const int *pd = (const int *)plan_dev.data_ptr();
 
-  rb::flash_dispatch_dh(DH, op, [&](auto dh) {
+  rb::flash_dispatch_win(DH, window, max_keys, op,
+                         [&](auto dh, auto win, int w) {
     constexpr int D = decltype(dh)::value;
-    auto kernel = vt ? flash_prefill_paged_batch_kernel<D, true>
-                     : flash_prefill_paged_batch_kernel<D, false>;
+    constexpr bool WIN = decltype(win)::value;
+    auto kernel = vt ? flash_prefill_paged_batch_kernel<D, true, WIN>
+                     : flash_prefill_paged_batch_kernel<D, false, WIN>;
     hipLaunchKernelGGL(kernel, grid, dim3(BLOCK), rb::flash_fwd_smem<D>(),
                        at::hip::getCurrentHIPStream(),
                        (const uint16_t *)q.data_ptr(),
@@ -363,7 +376,7 @@ at::Tensor flash_prefill_paged_batch(at::Tensor q, at::Tensor k_cache,
                        (const int *)block_tables.data_ptr(),
                        (uint16_t *)out.data_ptr(), pd, pd + (B + 1),
                        pd + (2 * B + 1), pd + (2 * B + 1 + ntiles), (int)maxb,
-                       (int)Hq, (int)Hkv, (float)scale);
+                       (int)Hq, (int)Hkv, (float)scale, w);
   });
   return out;
 }

@@ -55,13 +55,15 @@ std::vector<at::Tensor> paged_decode_swz(at::Tensor q, at::Tensor k_cache,
 at::Tensor paged_verify(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
                         at::Tensor block_tables, at::Tensor seq_lens,
                         at::Tensor q_lens, int64_t nsplit, double scale);
-at::Tensor flash_prefill(at::Tensor q, at::Tensor k, at::Tensor v, double scale);
+at::Tensor flash_prefill(at::Tensor q, at::Tensor k, at::Tensor v, double scale,
+                         int64_t window);
 at::Tensor flash_prefill_paged(at::Tensor q, at::Tensor k_cache, at::Tensor v_cache,
-                               at::Tensor block_table, int64_t ctx_len, double scale);
+                               at::Tensor block_table, int64_t ctx_len, double scale,
+                               int64_t window);
 at::Tensor flash_prefill_paged_batch(at::Tensor q, at::Tensor k_cache,
                                      at::Tensor v_cache, at::Tensor block_tables,
                                      at::Tensor plan_dev, at::Tensor plan_cpu,
-                                     int64_t B, double scale);
+                                     int64_t B, double scale, int64_t window);
 std::vector<at::Tensor> flash_fwd_train(at::Tensor q, at::Tensor k, at::Tensor v,
                                         double scale);
 std::vector<at::Tensor> fa_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
@@ -189,17 +191,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_tables"), py::arg("seq_lens"), py::arg("q_lens"),
         py::arg("nsplit"), py::arg("scale"));
-  m.def("flash_prefill", &flash_prefill, "MFMA flash-attention prefill (causal)");
+  m.def("flash_prefill", &flash_prefill,
+        "MFMA flash-attention prefill (causal; window = W >= 1: row p sees "
+        "keys (p - W, p])",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("window") = 0);
   m.def("flash_prefill_paged", &flash_prefill_paged,
         "MFMA flash-attention prefill of one chunk over the paged KV cache",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
-        py::arg("block_table"), py::arg("ctx_len"), py::arg("scale"));
+        py::arg("block_table"), py::arg("ctx_len"), py::arg("scale"),
+        py::arg("window") = 0);
   m.def("flash_prefill_paged_batch", &flash_prefill_paged_batch,
         "MFMA flash-attention prefill of several sequences' packed chunks "
         "over the paged KV cache",
         py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
         py::arg("block_tables"), py::arg("plan_dev"), py::arg("plan_cpu"),
-        py::arg("num_seqs"), py::arg("scale"));
+        py::arg("num_seqs"), py::arg("scale"), py::arg("window") = 0);
   m.def("flash_fwd_train", &flash_fwd_train,
         "MFMA flash-attention forward + log-sum-exp (training)");
   m.def("fa_bwd", &fa_bwd,

@@ -21,6 +21,19 @@
 // A row's result depends only on the sequence of 32-key sub-tiles from key
 // 0: a fully masked sub-tile is an exact no-op (alpha == 1, p == 0), so
 // where a workgroup's first row sits changes nothing.
+//
+// Sliding window (WIN, window = W >= 1): row p sees keys (p - W, p].
+//  * the workgroup's KV loop starts at tile kt0 = max(0, row0 - W + 1) / 64,
+//    the tile of the first key its first row sees: at most
+//    (256 + W) / 64 + 2 tiles are staged whatever S is, and no tile (for the
+//    paged sources: no block-table entry) in front of kt0 is touched.
+//  * a wave runs only the 32-key sub-tiles that overlap
+//    [first row - W + 1, last row]; both bounds sit in scalar registers.
+//  * the mask is one unsigned compare for both edges,
+//    (unsigned)(qrow - key) < W, in place of key <= qrow.
+// Keys staged in front of a row's window are masked in S, so their P is
+// exactly 0 and the property above holds from kt0 on: a row's result
+// depends only on W and on the 32-key sub-tiles that hold its window.
 #pragma once
 
 #include <type_traits>
@@ -34,6 +47,9 @@ namespace rb {
 
 constexpr int FLASH_BLOCK = 512;  // 8 waves
 constexpr int FLASH_KVB = 64;     // keys per LDS tile
+// windowed kernels: the running max of a row that has seen no key yet; far
+// below any score, and exp(FLASH_M_FLOOR - score) is exactly 0
+constexpr float FLASH_M_FLOOR = -1e30f;
 
 // dynamic LDS of one workgroup: K image [KVB][DH*2+16] + V^T image
 // [DH][KVB*2+16]
@@ -55,14 +71,15 @@ struct FlashAcc {
 //   qrow     its absolute position: keys [0, qrow] are visible
 //   S        keys exist at [0, S)
 //   row0     absolute position of the workgroup's first row
+//   window   WIN only: keys (qrow - window, qrow] are visible, window >= 1
 // KV is a struct with
 //   template <int DH> RB_DEV void stage(int kt, char *k_img, char *v_img) const
 // that fills the K image ([KVB][DH*2+16], row-major) and the V^T image
 // ([DH][KVB*2+16]) with keys [kt*KVB, kt*KVB + KVB), zeros at keys >= S.
-template <int DH, class KV>
+template <int DH, bool WIN = false, class KV>
 RB_DEV FlashAcc<DH> flash_fwd_rows(const uint16_t *q, int qrow, bool q_valid,
                                    int S, int row0, const KV &kv,
-                                   float scale) {
+                                   float scale, int window = 0) {
   constexpr int KVB = FLASH_KVB;
   constexpr int KSTEPS = DH / 16;       // QK^T contraction steps
   constexpr int DTILES = DH / 32;       // O column tiles
@@ -98,23 +115,37 @@ RB_DEV FlashAcc<DH> flash_fwd_rows(const uint16_t *q, int qrow, bool q_valid,
   float &m_run = acc.m, &l_run = acc.l;
 #pragma unroll
   for (int dt = 0; dt < DTILES; ++dt) acc_o[dt] = (f32x16v)(0.0f);
-  m_run = -INFINITY;
+  m_run = WIN ? FLASH_M_FLOOR : -INFINITY;
   l_run = 0.0f;
 
   const int kv_end = min(S, row0 + 256);  // causal upper bound for this WG
   const int n_tiles = (kv_end + KVB - 1) / KVB;
   const int wave_kmax = row0 + wid * 32 + 31;  // last key this wave can see
+  // WIN: the wave's key range [wk_lo, wk_hi] and the first tile, scalars
+  int kt0 = 0, wk_lo = 0, wk_hi = 0;
+  if constexpr (WIN) {
+    const int wrow0 = row0 + __builtin_amdgcn_readfirstlane(wid) * 32;
+    wk_lo = wrow0 - window + 1;
+    wk_hi = wrow0 + 31;
+    kt0 = max(0, row0 - window + 1) / KVB;
+  }
 
-  for (int kt = 0; kt < n_tiles; ++kt) {
+  for (int kt = kt0; kt < n_tiles; ++kt) {
     const int kbase = kt * KVB;
 
     kv.template stage<DH>(kt, k_img, v_img);
     __syncthreads();
 
-    if (kbase <= wave_kmax) {
+    if (WIN ? (kbase <= wk_hi && kbase + KVB - 1 >= wk_lo)
+            : (kbase <= wave_kmax)) {
       // two 32-key sub-tiles per LDS tile
 #pragma unroll
       for (int it = 0; it < 2; ++it) {
+        if constexpr (WIN) {
+          // a sub-tile no row of the wave sees is an exact no-op: skip it
+          if (kbase + it * 32 > wk_hi || kbase + it * 32 + 31 < wk_lo)
+            continue;
+        }
         // ---- QK^T^T: scores[key][qrow] ----------------------------------
         f32x16v s = (f32x16v)(0.0f);
 #pragma unroll
@@ -130,12 +161,22 @@ RB_DEV FlashAcc<DH> flash_fwd_rows(const uint16_t *q, int qrow, bool q_valid,
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int key = kbase + it * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-          p[r] = (key <= qrow) ? s[r] : -INFINITY;
+          const bool vis = WIN ? (unsigned)(qrow - key) < (unsigned)window
+                               : (key <= qrow);
+          p[r] = vis ? s[r] : -INFINITY;
           mx = fmaxf(mx, p[r]);
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));     // full row max
         const float mn = fmaxf(m_run, mx);
-        if (mn != -INFINITY) {
+        // Unwindowed, every row sees key 0, so the guard is wave-uniform.
+        // Windowed, rows of one wave meet their first visible key in
+        // different sub-tiles and the MFMAs below must not sit in a
+        // divergent branch: the body runs unguarded, and m_run starts at
+        // FLASH_M_FLOOR, so a row that has seen nothing takes the ordinary
+        // fully-masked path (alpha == 1, p == 0, an exact no-op) and its
+        // first visible key gives alpha == exp(floor - mn) == 0 exactly,
+        // the value the -inf start selects.
+        if (WIN || mn != -INFINITY) {
           const float alpha = (m_run == -INFINITY) ? 0.0f : __expf(m_run - mn);
           float psum = 0.0f;
 #pragma unroll
@@ -213,6 +254,24 @@ void flash_dispatch_dh(int64_t DH, const char *op, F &&f) {
   } else {
     TORCH_CHECK(false, op, ": DH must be 64, 128 or 256, got ", DH);
   }
+}
+
+// Host: head dim and window -> template arguments: f(dh, win, w) with win a
+// std::bool_constant and w the window to launch with. `window` is the
+// caller's (0 = none) and S the number of keys: a window that covers every
+// key is no window, and runs the unwindowed kernel (w = 0).
+template <class F>
+void flash_dispatch_win(int64_t DH, int64_t window, int64_t S, const char *op,
+                        F &&f) {
+  TORCH_CHECK(window >= 0, op, ": window must be >= 0, got ", window);
+  const int w = window >= S ? 0 : (int)window;
+  flash_dispatch_dh(DH, op, [&](auto dh) {
+    if (w == 0) {
+      f(dh, std::false_type{}, 0);
+    } else {
+      f(dh, std::true_type{}, w);
+    }
+  });
 }
 
 }  // namespace rb

@@ -25,16 +25,22 @@ on a prefix another member of the same batch is about to publish waits
 one step and hits; a prompt longer than ``prefill_chunk`` still takes the
 chunked path alone.
 
-Sliding-window attention (mistral, cfg.sliding_window): enforced here as
-pure KV bookkeeping — RoPE is applied at absolute positions when keys
-are written, so attention over any suffix of the cache is exact, and the
-kernel needs no window parameter. Whole front blocks that fall entirely
-outside the window are freed (bounded cache memory per sequence) and
-the block table / seq_len presented to the kernel cover only the
-retained suffix. Granularity is BLOCK_SIZE: a query attends to between
-W and W+BLOCK_SIZE-1 trailing tokens; prompts longer than W prefill
-with full causal attention (exact for prompts <= W, which covers the
-supported max prompt for mistral-7b).
+Sliding-window attention (mistral, cfg.sliding_window = W): every query
+attends to exactly its last W tokens, itself included, in prefill and in
+decode. RoPE is applied at absolute positions when keys are written, so
+attention over any suffix of the cache is exact. Decode is KV bookkeeping
+here: whole front blocks that fall entirely outside the window are freed
+(bounded cache memory per sequence), the block table / seq_len presented
+to the decode kernel cover only the retained suffix, and ``seq_starts``
+cuts the 0..BLOCK_SIZE-1 tokens of block slack. Prefill needs nothing
+from the engine: the model passes W to the prefill kernels (dense, paged,
+chunked and batched; ops/csrc/flash_fwd_core.h), which mask each row's
+keys in front of its window and skip the KV tiles in front of a
+workgroup's, so a prompt longer than W is exact and costs O(S W). No
+block is dropped while a prompt prefills (``dropped`` is 0, absolute and
+virtual positions coincide); ``_apply_window`` drops the front blocks
+before the first decode. Only the verify kernel is still full-attention,
+so ``speculative`` is ignored for a windowed model.
 """
 from __future__ import annotations
 
